@@ -3,7 +3,15 @@
 (BASELINE.json configs[1]) on N GPUs, plus the cosine top-k search leg (configs[4]),
 the ViT-L/14@336 leg (configs[3]) and the reference CPU path timed beside them.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and nothing else: it sets up, warms up, times
+--steps steps, writes the last step's embeddings if --dump-outputs DIR is given (DIR/image_embeds.npy,
+DIR/text_embeds.npy: float32, what encode_pair's caller receives; the inputs are seeded, so two
+builds can be compared output for output) and prints the result line. Everything else described
+below (roofline and its kernel trace, parity, the varlen / unmerged / other-dtype steps, the index
+build, search, per-item and L/14 legs, the CPU baselines) runs only with --full, where the
+--no-* options switch single legs off.
 
 --gpus N > 1 without a torch.distributed launcher around it: bench.py starts its own N ranks
 (python -m torch.distributed.run, 127.0.0.1) before touching the GPU and exits with their
@@ -75,6 +83,11 @@ def parse_args(argv=None):
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=256)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline step: roofline + kernel trace, parity, the other "
+                         "encode steps, index build, search, per-item, L/14 and CPU baseline legs (see --no-*)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's embeddings to DIR/image_embeds.npy and DIR/text_embeds.npy")
     ap.add_argument("--dtype", default="mixed", choices=["bfloat16", "float16", "mixed"])
     ap.add_argument("--lora-mode", default="merged", choices=["merged", "unmerged"])
     ap.add_argument("--cpu-budget", type=float, default=12.0, help="seconds of CPU encode timing")
@@ -1043,6 +1056,15 @@ def index_build_leg(dev, world: int, rank: int, n_images: int, batch: int, dtype
     return out
 
 
+def dump_outputs(out_dir: str, emb: torch.Tensor, B: int) -> None:
+    """The last timed step's results as its caller receives them: the L2-normalised float32 image and
+    text embeddings ([B, proj_dim] each; 1 MB together at the default batch), one .npy per array."""
+    os.makedirs(out_dir, exist_ok=True)
+    host = emb.detach().float().cpu().numpy()
+    np.save(os.path.join(out_dir, "image_embeds.npy"), host[:B])
+    np.save(os.path.join(out_dir, "text_embeds.npy"), host[B:])
+
+
 def main():
     args = parse_args()
     if args.trace_child:
@@ -1112,6 +1134,44 @@ def main():
         dt = float(t.item())
     ms_step = dt / args.steps * 1e3
     pairs_s = world * B / (dt / args.steps)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, emb, B)
+    fp = flops_per_pair(cfg, lora_merged=args.lora_mode == "merged")
+    step_flops = B * (fp["image"] + fp["caption"])
+    result = {
+        "metric": METRIC,
+        "value": round(pairs_s, 1),
+        "unit": "image+text pairs/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(ms_step, 4),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": DTYPE_LABEL[args.dtype],
+        "data": "synthetic (seeded uint8 224x224 RGB images, full 77-token id captions; deterministic synthetic weights)",
+        "config": {"workload": "ViT-B/32 + LoRA r=8 alpha=16 (q,k,v,out, both towers) encode + L2-normalise",
+                   "execution": "sequential" if args.sequential else
+                       f"image / text towers concurrently on 2 HIP streams (sub-batches per tower: {args.split or 1})"
+                       " + hipGraph replay",
+                   "per_gpu_batch": B, "global_batch": world * B, "seq_len": cfg.max_pos,
+                   "image_size": cfg.image_size, "lora_mode": args.lora_mode,
+                   "parallelism": f"dp{world}" + (" + all_gather(embeddings)" if world > 1 else "")},
+        "embeds_per_s": round(2 * pairs_s, 1),
+        "step_tflops_per_gpu": round(step_flops / (ms_step * 1e-3) / 1e12, 2),
+    }
+    if world > 1:
+        result["dist"] = {"backend": backend, "world_size": torch.distributed.get_world_size()}
+        if os.environ.get("CLM_REHEARSAL"):
+            result["rehearsal"] = os.environ["CLM_REHEARSAL"]
+    if not args.full:   # the plain run ends here: the headline figure and nothing beside it
+        model.close()
+        if rank == 0:
+            print(json.dumps(result), flush=True)
+        if world > 1:
+            torch.distributed.destroy_process_group()
+        return
 
     # profiled pass (outside the timed region): HIP events around every kernel launch
     model.prof_enable(True)
@@ -1123,10 +1183,8 @@ def main():
     prof = model.prof_read()
     model.prof_enable(False)
     gemm_ms, gemm_flops, gemm_n = prof["gemm"]
-    fp = flops_per_pair(cfg, lora_merged=args.lora_mode == "merged")
     pmc, pmc_src = pmc_summary()
     gemm_bytes = gemm_algorithmic_bytes(cfg, B) * nprof
-    step_flops = B * (fp["image"] + fp["caption"])
     trace = None
     if world == 1 and not args.no_trace and not args.sequential:
         try:
@@ -1153,66 +1211,39 @@ def main():
     else:
         dom, ach = None, seq_tf
 
-    result = {
-        "metric": METRIC,
-        "value": round(pairs_s, 1),
-        "unit": "image+text pairs/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(ms_step, 4),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": DTYPE_LABEL[args.dtype],
-        "data": "synthetic (seeded uint8 224x224 RGB images, full 77-token id captions; deterministic synthetic weights)",
-        "config": {"workload": "ViT-B/32 + LoRA r=8 alpha=16 (q,k,v,out, both towers) encode + L2-normalise",
-                   "execution": "sequential" if args.sequential else
-                       f"image / text towers concurrently on 2 HIP streams (sub-batches per tower: {args.split or 1})"
-                       " + hipGraph replay",
-                   "per_gpu_batch": B, "global_batch": world * B, "seq_len": cfg.max_pos,
-                   "image_size": cfg.image_size, "lora_mode": args.lora_mode,
-                   "parallelism": f"dp{world}" + (" + all_gather(embeddings)" if world > 1 else "")},
-        "embeds_per_s": round(2 * pairs_s, 1),
-        "step_tflops_per_gpu": round(step_flops / (ms_step * 1e-3) / 1e12, 2),
-        "roofline": {
-            "kernel": "gemm_kernel / gemm2_kernel / gemm_attn_kernel (MFMA 16x16x32: every encoder GEMM; "
-                      "the q/k/v GEMM fused with its attention, whose FLOPs it counts)",
-            "bound": "mfma",
-            "achieved": round(ach, 2),
-            "peak": MFMA_PEAK_TFLOPS,
-            "sustained_mfma_peak": {"value": MFMA_SUSTAINED_TFLOPS,
-                                    "frac": round(ach / MFMA_SUSTAINED_TFLOPS, 4),
-                                    "source": "tools/mfma_probe.hip: MFMA-only loop, random fp16 operands "
-                                              "(profiles/r03_v10_mfma_peak_probe.jsonl)"},
-            "unit": "TFLOP/s",
-            "frac": round(ach / MFMA_PEAK_TFLOPS, 4),
-            "dominant": dom,
-            "traffic": (dom or {}).get("pmc_hbm_bytes_per_launch") or pmc.get("gemm_mean_hbm_bytes_per_launch"),
-            "traffic_unit": "bytes per launch of the dominant kernel (PMC: 2*FETCH_SIZE + WRITE_SIZE, "
-                            "gfx950-corrected, tools/pmc.sh with the timed step's tile configs)",
-            "traffic_source": pmc_src,
-            "mfma_busy_frac": pmc.get("gemm_mfma_busy_frac"),
-            "mfma_busy_source": pmc_src if pmc.get("gemm_mfma_busy_frac") is not None else None,
-            "mode": ("achieved = the step's GEMM FLOPs / the time at least one GEMM kernel runs, per step, from a "
-                     "rocprofv3 kernel trace of the timed step's own form (two tower streams, hipGraph replay; "
-                     "`trace`); dominant = the GEMM kernel with the most time per step in that trace")
-                    if traced else "trace unavailable: per-kernel durations from the sequential profiled pass",
-            "trace": trace,
-            "sequential_pass": {"achieved": round(seq_tf, 2), "frac": round(seq_tf / MFMA_PEAK_TFLOPS, 4),
-                                "avg_launch_us": round(gemm_ms / gemm_n * 1e3, 2),
-                                "launches_per_step": gemm_n // nprof,
-                                "algorithmic_bytes_per_launch": round(gemm_bytes / max(gemm_n, 1)),
-                                "kernel_ms_per_step": {k: round(v[0] / nprof, 4) for k, v in prof.items()},
-                                "mode": "HIP events on the launch stream around every GEMM, towers one after the "
-                                        "other (no two kernels share the chip)"},
-            "step_frac": round(step_flops / (ms_step * 1e-3) / 1e12 / MFMA_PEAK_TFLOPS, 4),
-        },
+    result["roofline"] = {
+        "kernel": "gemm_kernel / gemm2_kernel / gemm_attn_kernel (MFMA 16x16x32: every encoder GEMM; "
+                  "the q/k/v GEMM fused with its attention, whose FLOPs it counts)",
+        "bound": "mfma",
+        "achieved": round(ach, 2),
+        "peak": MFMA_PEAK_TFLOPS,
+        "sustained_mfma_peak": {"value": MFMA_SUSTAINED_TFLOPS,
+                                "frac": round(ach / MFMA_SUSTAINED_TFLOPS, 4),
+                                "source": "tools/mfma_probe.hip: MFMA-only loop, random fp16 operands "
+                                          "(profiles/r03_v10_mfma_peak_probe.jsonl)"},
+        "unit": "TFLOP/s",
+        "frac": round(ach / MFMA_PEAK_TFLOPS, 4),
+        "dominant": dom,
+        "traffic": (dom or {}).get("pmc_hbm_bytes_per_launch") or pmc.get("gemm_mean_hbm_bytes_per_launch"),
+        "traffic_unit": "bytes per launch of the dominant kernel (PMC: 2*FETCH_SIZE + WRITE_SIZE, "
+                        "gfx950-corrected, tools/pmc.sh with the timed step's tile configs)",
+        "traffic_source": pmc_src,
+        "mfma_busy_frac": pmc.get("gemm_mfma_busy_frac"),
+        "mfma_busy_source": pmc_src if pmc.get("gemm_mfma_busy_frac") is not None else None,
+        "mode": ("achieved = the step's GEMM FLOPs / the time at least one GEMM kernel runs, per step, from a "
+                 "rocprofv3 kernel trace of the timed step's own form (two tower streams, hipGraph replay; "
+                 "`trace`); dominant = the GEMM kernel with the most time per step in that trace")
+                if traced else "trace unavailable: per-kernel durations from the sequential profiled pass",
+        "trace": trace,
+        "sequential_pass": {"achieved": round(seq_tf, 2), "frac": round(seq_tf / MFMA_PEAK_TFLOPS, 4),
+                            "avg_launch_us": round(gemm_ms / gemm_n * 1e3, 2),
+                            "launches_per_step": gemm_n // nprof,
+                            "algorithmic_bytes_per_launch": round(gemm_bytes / max(gemm_n, 1)),
+                            "kernel_ms_per_step": {k: round(v[0] / nprof, 4) for k, v in prof.items()},
+                            "mode": "HIP events on the launch stream around every GEMM, towers one after the "
+                                    "other (no two kernels share the chip)"},
+        "step_frac": round(step_flops / (ms_step * 1e-3) / 1e12 / MFMA_PEAK_TFLOPS, 4),
     }
-    if world > 1:
-        result["dist"] = {"backend": backend, "world_size": torch.distributed.get_world_size()}
-        if os.environ.get("CLM_REHEARSAL"):
-            result["rehearsal"] = os.environ["CLM_REHEARSAL"]
     if world == 1 and not args.no_varlen:
         try:
             result["varlen_text"] = varlen_leg(model, cfg, dev, B, imgs, args.steps, args.warmup, rank)

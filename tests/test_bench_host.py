@@ -88,3 +88,21 @@ def test_fold_sha256_sees_every_bit():
     c = a.clone()
     c[[3, 4]] = a[[4, 3]]                                            # two rows swapped
     assert fold_sha256(a) != fold_sha256(c)
+
+
+def test_plain_run_is_the_default(bench):
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert not a.full and a.dump_outputs is None and (a.steps, a.warmup) == (7, 2)
+    a = bench.parse_args(["--full", "--dump-outputs", "x"])
+    assert a.full and a.dump_outputs == "x"
+
+
+def test_dump_outputs_writes_both_towers(bench, tmp_path):
+    import numpy as np
+    g = torch.Generator().manual_seed(5)
+    emb = torch.randn((6, 16), generator=g)
+    d = tmp_path / "new" / "dir"
+    bench.dump_outputs(str(d), emb, 3)
+    img, txt = np.load(d / "image_embeds.npy"), np.load(d / "text_embeds.npy")
+    assert img.dtype == np.float32 and txt.dtype == np.float32
+    assert np.array_equal(img, emb[:3].numpy()) and np.array_equal(txt, emb[3:].numpy())

@@ -143,7 +143,7 @@ def test_rccl_collectives(tmp_path):
 def test_bench_spawns_its_own_ranks(tmp_path):
     """bench.py --gpus 2 with no launcher around it starts 2 ranks itself (gloo rehearsal on a
     1-GPU box) and reports n_gpus 2 from a 2-rank process group."""
-    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "1",
            "--batch", "32", "--no-cpu-baseline", "--no-l14", "--no-parity-mode", "--search-rows", "600000",
            "--search-queries", "256"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=str(tmp_path))

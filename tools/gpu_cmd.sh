@@ -5,7 +5,7 @@ cd "$(dirname "$0")/.." && export TMPDIR=/tmp && mkdir -p gpurun_out/ab
 for rep in 1 2; do
   for arm in A B C D; do
     case $arm in A) envs="";; B) envs="CLM_SCAN_NW=2 CLM_SCAN_D=4";; C) envs="CLM_SCAN_NW=2 CLM_SCAN_D=2";; D) envs="CLM_SCAN_NW=4 CLM_SCAN_D=2";; esac
-    env $envs timeout -k 10 400 python bench.py --no-cpu-baseline --no-l14 --no-varlen --no-index-build --no-unmerged --no-parity-mode \
+    env $envs timeout -k 10 400 python bench.py --full --no-cpu-baseline --no-l14 --no-varlen --no-index-build --no-unmerged --no-parity-mode \
       --no-trace --no-encode-item --no-near-dup --no-persist > gpurun_out/ab/w$arm.$rep.json 2> gpurun_out/ab/w$arm.$rep.err
     rc=$?; [ $rc -eq 0 ] || { tail -5 gpurun_out/ab/w$arm.$rep.err; exit $rc; }
     python -c "
