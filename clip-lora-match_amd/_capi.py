@@ -88,6 +88,11 @@ def lib():
                                    c_void_p]),
         "clm_topk_threshold": (c_int, [c_int, c_void_p, c_int64, c_int64, c_int64, c_int, ctypes.c_float, c_int,
                                        c_void_p, c_void_p]),
+        "clm_scan16": (c_int, [c_int, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int64,
+                               c_void_p, c_void_p, c_int64, c_void_p]),
+        "clm_scan16_waves": (c_int64, [c_int, c_int64, c_int]),
+        "clm_collect_ge": (c_int, [c_int, c_void_p, c_int, c_int, c_int64, c_void_p, c_void_p, c_int, c_void_p,
+                                   c_void_p, c_int64, c_void_p]),
         "clm_l2_normalize": (c_int, [c_int, c_void_p, c_int64, c_int, c_void_p]),
         "clm_fuse_queries": (c_int, [c_int, c_void_p, ctypes.c_float, c_void_p, ctypes.c_float, c_int64, c_int,
                                      c_void_p, c_void_p]),
@@ -131,6 +136,7 @@ EXPORTED = (
     "clm_last_error", "clm_version",
     "clm_model_desc_size", "clm_prof_enable", "clm_prof_read", "clm_gemm", "clm_gemm_num_configs",
     "clm_attention", "clm_attention_ex", "clm_gemm_scores16", "clm_layernorm", "clm_debug_set",
+    "clm_scan16", "clm_scan16_waves", "clm_collect_ge",
 )
 CLM_EPI_STORE, CLM_EPI_GELU, CLM_EPI_RESID, CLM_EPI_SCORE = 0, 1, 2, 4
 CLM_PROF_GEMM, CLM_PROF_ATTN, CLM_PROF_LN, CLM_PROF_OTHER = 0, 1, 2, 3

@@ -1361,15 +1361,16 @@ static int index_grow(clm_index* x, int64_t need_rows) {
   return CLM_OK;
 }
 
-// rescore_select / topk_merge order ties by a 32-bit image of the global row index
-constexpr int64_t MAX_GLOBAL_ROWS = (int64_t)0xFFFFFFFF;
+// rescore_select / topk_merge / topk_any order ties by a 32-bit image of the row's index inside
+// its own index (the global offset is added after the selection, so any offset orders alike)
+constexpr int64_t MAX_INDEX_ROWS = (int64_t)0xFFFFFFFF;
+constexpr int64_t MAX_GLOBAL_OFFSET = (int64_t)1 << 62;
 
 int clm_index_append(clm_index* x, const void* rows, int dtype, int64_t n, void* stream) {
   if (!x || n < 0 || (n > 0 && !rows)) return fail(CLM_E_ARG, "bad argument");
   if (dtype != CLM_F32 && dtype != CLM_F16) return fail(CLM_E_ARG, "rows must be f32 or f16");
   if (n == 0) return CLM_OK;
-  if (x->offset + x->n + n > MAX_GLOBAL_ROWS)
-    return fail(CLM_E_ARG, "index append: global row indices must stay below 2^32 (offset + rows)");
+  if (x->n + n > MAX_INDEX_ROWS) return fail(CLM_E_ARG, "index append: one index holds fewer than 2^32 rows");
   DeviceGuard g(x->dev);
   hipStream_t st = (hipStream_t)stream;
   HIPCHK(hipStreamSynchronize(st));
@@ -1445,8 +1446,7 @@ int clm_index_import(clm_index* x, const uint16_t* rows16, const float* inv, con
                      void* stream) {
   if (!x || n < 0 || (n > 0 && (!rows16 || !inv))) return fail(CLM_E_ARG, "index import: bad argument");
   if (n == 0) return CLM_OK;
-  if (x->offset + x->n + n > MAX_GLOBAL_ROWS)
-    return fail(CLM_E_ARG, "index import: global row indices must stay below 2^32 (offset + rows)");
+  if (x->n + n > MAX_INDEX_ROWS) return fail(CLM_E_ARG, "index import: one index holds fewer than 2^32 rows");
   DeviceGuard g(x->dev);
   hipStream_t st = (hipStream_t)stream;
   HIPCHK(hipStreamSynchronize(st));
@@ -1487,9 +1487,7 @@ int clm_index_reset(clm_index* x) {
 }
 
 int clm_index_set_offset(clm_index* x, int64_t off) {
-  if (!x || off < 0) return fail(CLM_E_ARG, "bad argument");
-  if (off + x->n > MAX_GLOBAL_ROWS)
-    return fail(CLM_E_ARG, "index offset: global row indices must stay below 2^32 (offset + rows)");
+  if (!x || off < 0 || off > MAX_GLOBAL_OFFSET) return fail(CLM_E_ARG, "index offset: 0 <= offset <= 2^62");
   x->offset = off;
   return CLM_OK;
 }
@@ -1767,13 +1765,16 @@ static int overflow_wide(clm_index* x, const std::vector<int64_t>& qs, const std
   return CLM_OK;
 }
 
+static int exact_redo(clm_index* x, const std::vector<int64_t>& full, const float* q32, const double* qn, int k,
+                      float* osc, int64_t* oix, hipStream_t st);
+
 // Candidate lists that overflowed CAND_CAP (queries `overflow`, first-pass counts `ocount`): rebuilt
 // whole by a second filter pass (overflow_wide) or redone by the exact scan (search_bounded,
-// search_small). th: every query's filter threshold.
+// search_small). th: every query's filter threshold. `exact`: further queries for that one exact scan.
 static int finish_overflow(clm_index* x, const std::vector<int64_t>& overflow, const std::vector<int64_t>& ocount,
                            const u16* q16, const float* qinv, const float* q32, const double* qn, const float* th,
-                           int k, float* osc, int64_t* oix, hipStream_t st) {
-  const int dim = (int)x->dim;
+                           int k, float* osc, int64_t* oix, hipStream_t st,
+                           const std::vector<int64_t>* exact = nullptr) {
   int r;
   // Candidate lists beyond CAND_CAP (near-duplicate rows inside the window). Lists of up to
   // (SORT_MAX / k) chunks are rebuilt whole by a second filter pass over just those queries and
@@ -1781,6 +1782,7 @@ static int finish_overflow(clm_index* x, const std::vector<int64_t>& overflow, c
   // ONE scan (the index is streamed once per query block of search_scan, not once per query).
   x->search_stats[2] += (int64_t)overflow.size();
   std::vector<int64_t> wide, wcount, full;
+  if (exact) full = *exact;
   for (size_t j = 0; j < overflow.size(); ++j) {
     // headroom over the first pass's count: a different tile shape may round a score differently
     const int64_t cap2 = ocount[j] + ocount[j] / 8 + 256;
@@ -1792,6 +1794,15 @@ static int finish_overflow(clm_index* x, const std::vector<int64_t>& overflow, c
     }
   }
   if (!wide.empty() && (r = overflow_wide(x, wide, wcount, q16, qinv, q32, qn, th, k, osc, oix, full, st))) return r;
+  return exact_redo(x, full, q32, qn, k, osc, oix, st);
+}
+
+// Queries `full` of a batch redone by the exact scan, all of them in one scan; their rows of
+// osc / oix are replaced.
+static int exact_redo(clm_index* x, const std::vector<int64_t>& full, const float* q32, const double* qn, int k,
+                      float* osc, int64_t* oix, hipStream_t st) {
+  const int dim = (int)x->dim;
+  int r;
   if (full.empty()) return CLM_OK;
   const int64_t no = (int64_t)full.size();
   size_t o2 = 0;
@@ -2071,15 +2082,21 @@ static int search_small(clm_index* x, const u16* q16, const float* qinv, const f
   std::vector<int> hcnt(nq);
   HIPCHK(hipMemcpyAsync(hcnt.data(), cnt, (size_t)nq * 4, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
-  std::vector<int64_t> overflow, ocount;
+  // fewer than k candidates although the index holds k rows (nchunk >= k): scores that are NaN (a
+  // zero or non-finite query; fewer than k rows with a finite norm) never pass score >= th, and
+  // no threshold describes such a top-k: the exact scan, which defines the result, serves it
+  std::vector<int64_t> overflow, ocount, degenerate;
   for (int64_t i = 0; i < nq; ++i)
     if (hcnt[i] > CAND_CAP) {
       overflow.push_back(i);
       ocount.push_back(hcnt[i]);
+    } else if (hcnt[i] < k) {
+      degenerate.push_back(i);
     }
-  x->search_stats[6] += nq - (int64_t)overflow.size();
-  if (overflow.empty()) return CLM_OK;
-  return finish_overflow(x, overflow, ocount, q16, qinv, q32, qn, th, k, osc, oix, st);
+  x->search_stats[6] += nq - (int64_t)overflow.size() - (int64_t)degenerate.size();
+  x->search_stats[1] += (int64_t)degenerate.size();
+  if (overflow.empty() && degenerate.empty()) return CLM_OK;
+  return finish_overflow(x, overflow, ocount, q16, qinv, q32, qn, th, k, osc, oix, st, &degenerate);
 }
 
 // Top-k by EXACT cosine (the fp32-rounded fp64 cosine of the caller's query and rows), order
@@ -2250,6 +2267,47 @@ int clm_topk_threshold(int hip_device, const float* scores, int64_t lds, int64_t
   return CLM_OK;
 }
 
+int clm_scan16(int hip_device, const uint16_t* rows16, const float* inv, int64_t N, int dim, const uint16_t* q16,
+               const float* qinv, int nq, float* out, int64_t ldo, float* cmax, float* wtop, int64_t ldw,
+               void* stream) {
+  if (N < 0 || nq < 0) return fail(CLM_E_ARG, "scan16: bad shape");
+  if (N == 0 || nq == 0) return CLM_OK;
+  if (!is_device_ptr(rows16) || !is_device_ptr(inv) || !is_device_ptr(q16) || !is_device_ptr(qinv) ||
+      !is_device_ptr(out) || !is_device_ptr(cmax) || (wtop && !is_device_ptr(wtop)))
+    return fail(CLM_E_ARG, "scan16: device pointers");
+  DeviceGuard g(hip_device);
+  Scan16Args a{};
+  a.rows = rows16; a.inv = inv; a.N = N; a.dim = dim;
+  a.q16 = q16; a.qinv = qinv; a.nq = nq;
+  a.out = out; a.ldo = ldo; a.cmax = cmax; a.nchunk = (N + 255) / 256;
+  a.wtop = wtop; a.ldw = ldw;
+  const hipError_t e = scan16(a, (hipStream_t)stream);
+  if (e == hipErrorInvalidValue)
+    return fail(CLM_E_ARG, "scan16: dim % 64 == 0 in [64, 1024], nq <= 16, ldo a power of two in [nq, 16], ldw >= 8 waves");
+  if (e != hipSuccess) return fail(CLM_E_HIP, std::string("scan16: ") + hipGetErrorString(e));
+  return CLM_OK;
+}
+
+int64_t clm_scan16_waves(int hip_device, int64_t N, int dim) {
+  DeviceGuard g(hip_device);
+  return scan16_waves((std::max<int64_t>(N, 0) + 255) / 256, dim);
+}
+
+int clm_collect_ge(int hip_device, const float* scores, int ldq, int nq, int64_t C, const float* th, int* cnt, int cap,
+                   float* cand_s, int64_t* cand_i, int64_t base, void* stream) {
+  if (nq < 0 || C < 0 || cap < 0) return fail(CLM_E_ARG, "collect_ge: bad shape");
+  if (nq == 0 || C == 0) return CLM_OK;
+  if (!is_device_ptr(scores) || !is_device_ptr(th) || !is_device_ptr(cnt) || !is_device_ptr(cand_s) ||
+      !is_device_ptr(cand_i))
+    return fail(CLM_E_ARG, "collect_ge: device pointers");
+  DeviceGuard g(hip_device);
+  const hipError_t e = collect_ge(scores, ldq, nq, C, th, cnt, cap, cand_s, cand_i, base, (hipStream_t)stream);
+  if (e == hipErrorInvalidValue)
+    return fail(CLM_E_ARG, "collect_ge: ldq a power of two in [nq, 16], scores 16-byte aligned");
+  if (e != hipSuccess) return fail(CLM_E_HIP, std::string("collect_ge: ") + hipGetErrorString(e));
+  return CLM_OK;
+}
+
 int clm_topk_merge(int hip_device, const float* scores, const int64_t* idx, int64_t nq, int parts, int k_in, int k,
                    float* out_scores, int64_t* out_idx, void* stream) {
   if (nq < 0 || parts <= 0 || k_in <= 0 || k <= 0 || (int64_t)parts * k_in > 0x7FFFFFFF)
@@ -2268,7 +2326,7 @@ int clm_topk_merge(int hip_device, const float* scores, const int64_t* idx, int6
   // +512 slack under-allocated 4 small takes -- found by the host-sanitizer harness)
   const size_t bytes = (in_d ? 0 : round_up(n_in * 4, 256) + round_up(n_in * 8, 256)) +
                        (out_d ? 0 : round_up((size_t)nq * k * 4, 256) + round_up((size_t)nq * k * 8, 256)) +
-                       (any ? round_up(topk_any_ws_bytes(any_rows, k), 256) : 0);
+                       (any ? round_up(topk_any_ws_bytes(any_rows, k), 256) + 256 : 0);
   Scratch& scr = scratch_of_current_device();
   std::unique_lock<std::mutex> lock(scr.mu, std::defer_lock);
   if (bytes > 0) {   // host lists: staged through the device scratch (the call drains its stream)
@@ -2296,6 +2354,16 @@ int clm_topk_merge(int hip_device, const float* scores, const int64_t* idx, int6
   } else {
     void* aws = take(topk_any_ws_bytes(any_rows, k));
     const int64_t n_row = (int64_t)parts * k_in;
+    // past one LDS sort the selection keys hold the low 32 bits of an index: larger ones are refused
+    int64_t* mx = (int64_t*)take(8);
+    int64_t hmx = 0;
+    if (e == hipSuccess) e = max_index(i_in, (int64_t)n_in, mx, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(&hmx, mx, 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e == hipSuccess && hmx > (int64_t)0xFFFFFFFF) {
+      scratch_trim(scr);
+      return fail(CLM_E_ARG, "topk_merge: more than 8192 candidates per query or k > 1024 needs indices below 2^32");
+    }
     for (int64_t q0 = 0; e == hipSuccess && q0 < nq; q0 += any_rows)
       e = topk_any(s_in + q0 * n_row, n_row, i_in + q0 * n_row, n_row, std::min(any_rows, nq - q0), n_row, k, 0,
                    s_out + q0 * k, i_out + q0 * k, k, aws, st);

@@ -69,6 +69,12 @@ static void argument_checks() {
   CHECK(clm_layernorm(0, CLM_BF16, nullptr, 100, 4, 100, nullptr, nullptr, 1e-5f, nullptr, 100, nullptr) == CLM_E_ARG);
   CHECK(clm_topk_merge(0, nullptr, nullptr, 1, 0, 1, 1, nullptr, nullptr, nullptr) != CLM_OK);
   CHECK(clm_l2_normalize(0, nullptr, 1, 0, nullptr) != CLM_OK);
+  CHECK(clm_scan16(0, nullptr, nullptr, -1, 64, nullptr, nullptr, 1, nullptr, 1, nullptr, nullptr, 0, nullptr) ==
+        CLM_E_ARG);
+  CHECK(clm_scan16(0, nullptr, nullptr, 256, 64, nullptr, nullptr, 1, nullptr, 1, nullptr, nullptr, 0, nullptr) ==
+        CLM_E_ARG);   // not device pointers
+  CHECK(clm_collect_ge(0, nullptr, 1, -1, 1, nullptr, nullptr, 1, nullptr, nullptr, 0, nullptr) == CLM_E_ARG);
+  CHECK(clm_index_set_offset(nullptr, 0) == CLM_E_ARG);
 }
 
 static double cos64(const float* a, const float* b, int dim) {

@@ -267,7 +267,7 @@ __global__ __launch_bounds__(NT) void rescore_select_kernel(const float* cs, con
   for (int j = threadIdx.x; j < n2; j += NT) {
     uint64_t v = 0;
     if (j < c) {
-      const int64_t ix = ci[row * cap + j];
+      const int64_t ix = ci[row * cap + j] - offset;   // local row: < 2^32 whatever the offset
       v = ((uint64_t)fkey(cs[row * cap + j]) << 32) | (uint64_t)(0xFFFFFFFFu - (uint32_t)ix);
     }
     keys[j] = v;
@@ -288,9 +288,9 @@ __global__ __launch_bounds__(NT) void rescore_select_kernel(const float* cs, con
   const double qnr = qn[row];
   for (int j = wid; j < m; j += NT / 64) {
     const uint32_t low = (uint32_t)(keys[j] & 0xFFFFFFFFu);
-    const int64_t gix = (int64_t)(0xFFFFFFFFu - low);
+    const int64_t lix = (int64_t)(0xFFFFFFFFu - low);
     double d, rr;
-    dot_wave(qr, rows + (gix - offset) * dim, dim, lane, d, rr);
+    dot_wave(qr, rows + lix * dim, dim, lane, d, rr);
     const float sc = cos_from(d, qnr, rr);
     if (lane == 0) keys[j] = ((uint64_t)fkey(sc) << 32) | low;
   }
@@ -304,7 +304,7 @@ __global__ __launch_bounds__(NT) void rescore_select_kernel(const float* cs, con
     if (j < m) {
       const uint64_t v = keys[j];
       os[row * k + j] = kfloat((uint32_t)(v >> 32));
-      oi[row * k + j] = (int64_t)(0xFFFFFFFFu - (uint32_t)(v & 0xFFFFFFFFu));
+      oi[row * k + j] = offset + (int64_t)(0xFFFFFFFFu - (uint32_t)(v & 0xFFFFFFFFu));
     } else {
       os[row * k + j] = -INFINITY;
       oi[row * k + j] = -1;
@@ -333,11 +333,11 @@ __global__ __launch_bounds__(NT) void rescore_wide_kernel(const int64_t* ci, con
   const float* qr = q + row * dim;
   const double qnr = qn[row];
   for (int j = wid; j < n; j += NT / 64) {
-    const int64_t gix = ci[row * cap + j0 + j];
+    const int64_t lix = ci[row * cap + j0 + j] - offset;   // local row
     double d, rr;
-    dot_wave(qr, rows + (gix - offset) * dim, dim, lane, d, rr);
+    dot_wave(qr, rows + lix * dim, dim, lane, d, rr);
     const float sc = cos_from(d, qnr, rr);
-    if (lane == 0) keys[j] = ((uint64_t)fkey(sc) << 32) | (uint64_t)(0xFFFFFFFFu - (uint32_t)gix);
+    if (lane == 0) keys[j] = ((uint64_t)fkey(sc) << 32) | (uint64_t)(0xFFFFFFFFu - (uint32_t)lix);
   }
   int n2 = 1;
   while (n2 < n) n2 <<= 1;
@@ -350,7 +350,7 @@ __global__ __launch_bounds__(NT) void rescore_wide_kernel(const int64_t* ci, con
     if (j < n) {
       const uint64_t v = keys[j];
       o_s[j] = kfloat((uint32_t)(v >> 32));
-      o_i[j] = (int64_t)(0xFFFFFFFFu - (uint32_t)(v & 0xFFFFFFFFu));
+      o_i[j] = offset + (int64_t)(0xFFFFFFFFu - (uint32_t)(v & 0xFFFFFFFFu));
     } else {
       o_s[j] = -INFINITY;
       o_i[j] = -1;
@@ -488,28 +488,59 @@ __global__ void upcast_f16_kernel(const u16* src, int64_t total, float* dst) {
     dst[i] = f16_to_f32(src[i]);
 }
 
+// Indices are full 64-bit values (shards of any global offset): the LDS sort orders (score key,
+// list position); every entry of a group of equal scores that starts inside the top k then takes
+// the group's first position plus the number of members with a smaller index (equal indices: the
+// earlier list position first), so the output order is (score desc, index asc) exactly. Groups are
+// single entries except for duplicated rows.
 __global__ __launch_bounds__(NT) void topk_merge_kernel(const float* in_s, const int64_t* in_i, int n_in,
                                                         int k, float* os, int64_t* oi) {
   __shared__ uint64_t cand[SORT_MAX];
   const int64_t row = blockIdx.x;
+  const int64_t* ri = in_i + row * n_in;
   int n2 = 1;
   while (n2 < n_in) n2 <<= 1;
   for (int j = threadIdx.x; j < n2; j += NT) {
     uint64_t v = 0;
-    if (j < n_in) {
-      const int64_t ix = in_i[row * n_in + j];
-      if (ix >= 0)
-        v = ((uint64_t)fkey(in_s[row * n_in + j]) << 32) | (uint64_t)(0xFFFFFFFFu - (uint32_t)ix);
-    }
+    if (j < n_in && ri[j] >= 0)
+      v = ((uint64_t)fkey(in_s[row * n_in + j]) << 32) | (uint64_t)(0xFFFFFFFFu - (uint32_t)j);
     cand[j] = v;
   }
   __syncthreads();
   if (n2 > 1) bitonic_desc(cand, n2);
-  for (int j = threadIdx.x; j < k; j += NT) {
-    const uint64_t v = j < n_in ? cand[j] : 0;
-    if (v == 0) { os[row * k + j] = -INFINITY; oi[row * k + j] = -1; continue; }
-    os[row * k + j] = kfloat((uint32_t)(v >> 32));
-    oi[row * k + j] = (int64_t)(0xFFFFFFFFu - (uint32_t)(v & 0xFFFFFFFFu));
+  auto key_at = [&](int j) { return (uint32_t)(cand[j] >> 32); };
+  auto pos_at = [&](int j) { return (int)(0xFFFFFFFFu - (uint32_t)(cand[j] & 0xFFFFFFFFu)); };
+  const int jmax = max(n2, k);
+  for (int j = threadIdx.x; j < jmax; j += NT) {
+    const uint64_t v = j < n2 ? cand[j] : 0;
+    if (v == 0) {   // past the valid entries (they sort last)
+      if (j < k) { os[row * k + j] = -INFINITY; oi[row * k + j] = -1; }
+      continue;
+    }
+    const uint32_t key = key_at(j);
+    const int pos = pos_at(j);
+    const int64_t ix = ri[pos];
+    int rank = j;
+    const bool tied = (j > 0 && key_at(j - 1) == key) || (j + 1 < n2 && cand[j + 1] != 0 && key_at(j + 1) == key);
+    if (tied) {
+      int s = j;
+      while (s > 0 && key_at(s - 1) == key) --s;
+      if (s < k) {
+        rank = s;
+        for (int m = s; m < n2 && cand[m] != 0 && key_at(m) == key; ++m) {
+          if (m == j) continue;
+          const int pm = pos_at(m);
+          const int64_t im = ri[pm];
+          rank += (im < ix) || (im == ix && pm < pos);
+        }
+      } else {
+        rank = k;
+      }
+    }
+    if (rank < k) {
+      os[row * k + rank] = kfloat(key);
+      oi[row * k + rank] = ix;
+    }
   }
 }
 // ---- top-k for any k (topk_any: k > 1024, or more merge candidates than one LDS sort holds) ----------
@@ -528,8 +559,9 @@ __global__ __launch_bounds__(NT) void topk_merge_kernel(const float* in_s, const
 constexpr int RUN = 8192;
 
 __device__ __forceinline__ bool any_valid(const int64_t* ix, int64_t j) { return !ix || ix[j] >= 0; }
-__device__ __forceinline__ uint32_t any_lo(const int64_t* ix, int64_t base, int64_t j) {
-  return 0xFFFFFFFFu - (uint32_t)(ix ? ix[j] : base + j);
+// low word: the list's index, or the column (emit_kernel adds the base, so any base orders alike)
+__device__ __forceinline__ uint32_t any_lo(const int64_t* ix, int64_t j) {
+  return 0xFFFFFFFFu - (uint32_t)(ix ? ix[j] : j);
 }
 
 // radix select over `get(i, v)` (true: entry i takes part with 32-bit value v) of the kk-th largest
@@ -584,7 +616,7 @@ __device__ void radix_kth(int64_t C, int kk, uint32_t* hist, uint32_t& s_prefix,
 }
 
 __global__ __launch_bounds__(NT) void kth_exact_kernel(const float* S, int64_t lds, const int64_t* I, int64_t ldi,
-                                                       int64_t C, int k, int64_t base, uint32_t* thr) {
+                                                       int64_t C, int k, uint32_t* thr) {
   __shared__ uint32_t hist[2048];
   __shared__ uint32_t s_prefix;
   __shared__ int s_pbits, s_kk;
@@ -617,15 +649,14 @@ __global__ __launch_bounds__(NT) void kth_exact_kernel(const float* S, int64_t l
   __syncthreads();
   radix_kth(C, need, hist, s_prefix, s_pbits, s_kk, [&](int64_t i, uint32_t& v) {
     if (!any_valid(ix, i) || fkey(s[i]) != T) return false;
-    v = any_lo(ix, base, i);
+    v = any_lo(ix, i);
     return true;
   });
   if (threadIdx.x == 0) { thr[2 * row] = T; thr[2 * row + 1] = s_prefix; }
 }
 
 __global__ __launch_bounds__(NT) void collect_kernel(const float* S, int64_t lds, const int64_t* I, int64_t ldi,
-                                                     int64_t C, int64_t base, const uint32_t* thr, uint64_t* seg,
-                                                     int64_t Kp) {
+                                                     int64_t C, const uint32_t* thr, uint64_t* seg, int64_t Kp) {
   __shared__ int s_n;
   const int64_t row = blockIdx.x;
   const float* s = S + row * lds;
@@ -637,7 +668,7 @@ __global__ __launch_bounds__(NT) void collect_kernel(const float* S, int64_t lds
   const uint64_t lim = ((uint64_t)thr[2 * row] << 32) | thr[2 * row + 1];
   for (int64_t i = threadIdx.x; i < C; i += NT) {
     if (!any_valid(ix, i)) continue;
-    const uint64_t comp = ((uint64_t)fkey(s[i]) << 32) | any_lo(ix, base, i);
+    const uint64_t comp = ((uint64_t)fkey(s[i]) << 32) | any_lo(ix, i);
     if (comp >= lim) {
       const int at = atomicAdd(&s_n, 1);
       if (at < Kp) out[at] = comp;
@@ -673,8 +704,8 @@ __global__ __launch_bounds__(256) void merge_runs_kernel(const uint64_t* src, ui
   }
 }
 
-__global__ __launch_bounds__(256) void emit_kernel(const uint64_t* seg, int64_t Kp, int64_t nq, int k, float* os,
-                                                   int64_t* oi, int64_t ldo) {
+__global__ __launch_bounds__(256) void emit_kernel(const uint64_t* seg, int64_t Kp, int64_t nq, int k, int64_t base,
+                                                   float* os, int64_t* oi, int64_t ldo) {
   const int64_t total = nq * k;
   for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < total; p += (int64_t)gridDim.x * 256) {
     const int64_t row = p / k, j = p - row * k;
@@ -684,7 +715,7 @@ __global__ __launch_bounds__(256) void emit_kernel(const uint64_t* seg, int64_t 
       oi[row * ldo + j] = -1;
     } else {
       os[row * ldo + j] = kfloat((uint32_t)(v >> 32));
-      oi[row * ldo + j] = (int64_t)(0xFFFFFFFFu - (uint32_t)(v & 0xFFFFFFFFu));
+      oi[row * ldo + j] = base + (int64_t)(0xFFFFFFFFu - (uint32_t)(v & 0xFFFFFFFFu));
     }
   }
 }
@@ -709,8 +740,8 @@ hipError_t topk_any(const float* scores, int64_t lds, const int64_t* idx, int64_
   uint32_t* thr = (uint32_t*)ws;   // per row {T, Lo}
   uint64_t* seg = (uint64_t*)(((uintptr_t)(thr + 2 * nq) + 255) & ~(uintptr_t)255);
   uint64_t* seg2 = seg + nq * kp;
-  kth_exact_kernel<<<(unsigned)nq, NT, 0, s>>>(scores, lds, idx, ldi, C, k, base, thr);
-  collect_kernel<<<(unsigned)nq, NT, 0, s>>>(scores, lds, idx, ldi, C, base, thr, seg, kp);
+  kth_exact_kernel<<<(unsigned)nq, NT, 0, s>>>(scores, lds, idx, ldi, C, k, thr);
+  collect_kernel<<<(unsigned)nq, NT, 0, s>>>(scores, lds, idx, ldi, C, thr, seg, kp);
   const int run = (int)std::min<int64_t>(kp, RUN);
   sort_runs_kernel<<<dim3((unsigned)(kp / run), (unsigned)nq), NT, 0, s>>>(seg, kp, run);
   uint64_t *a = seg, *b = seg2;
@@ -719,7 +750,8 @@ hipError_t topk_any(const float* scores, int64_t lds, const int64_t* idx, int64_
     merge_runs_kernel<<<(unsigned)std::min<int64_t>((total + 255) / 256, 65536), 256, 0, s>>>(a, b, kp, L, total);
     std::swap(a, b);
   }
-  emit_kernel<<<(unsigned)std::min<int64_t>((nq * k + 255) / 256, 65536), 256, 0, s>>>(a, kp, nq, k, out_s, out_i, ldo);
+  emit_kernel<<<(unsigned)std::min<int64_t>((nq * k + 255) / 256, 65536), 256, 0, s>>>(a, kp, nq, k, idx ? 0 : base, out_s,
+                                                                                        out_i, ldo);
   return hipGetLastError();
 }
 
@@ -807,6 +839,22 @@ hipError_t topk_rows(const float* scores, int64_t lds, int64_t nq, int64_t C, in
   if (nq <= 0) return hipSuccess;
   if (k < 1 || k > 1024 || C < 0 || C > 0xFFFFFFFFll) return hipErrorInvalidValue;
   topk_rows_kernel<<<(unsigned)nq, NT, 0, s>>>(scores, lds, C, k, base, out_s, out_i, ldo);
+  return hipGetLastError();
+}
+
+namespace {
+__global__ __launch_bounds__(256) void max_index_kernel(const int64_t* ix, int64_t n, unsigned long long* out) {
+  int64_t m = -1;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) m = max(m, ix[i]);
+  if (m >= 0) atomicMax(out, (unsigned long long)m);
+}
+}  // namespace
+
+hipError_t max_index(const int64_t* idx, int64_t n, int64_t* out, hipStream_t s) {
+  hipError_t e = hipMemsetAsync(out, 0, 8, s);
+  if (e != hipSuccess || n <= 0) return e;
+  const int blocks = (int)std::min<int64_t>((n + 255) / 256, 2048);
+  max_index_kernel<<<blocks, 256, 0, s>>>(idx, n, (unsigned long long*)out);
   return hipGetLastError();
 }
 
@@ -961,6 +1009,32 @@ constexpr int SCAN_CHUNK = 256;
 #ifndef CLM_SCAN_AUX
 #define CLM_SCAN_AUX 2
 #endif
+// LDS placement of 16-byte piece p of row r in a 16-row block image (rows of KS * 64 bytes, 4 KS
+// pieces): the piece index XORed with a per-row mask, so that 16 consecutive rows at one piece
+// position land on 16 distinct bank quads. The mask must stay inside the row: 4 bits (r & 15)
+// only where the piece count is a multiple of 16 (dim % 128 == 0); elsewhere the count is an odd
+// multiple of 8 and the row stride an odd multiple of 128 B, so rows alternate between the two
+// halves of the 256-B bank line and the 3-bit mask (r >> 1) & 7 separates the 8 rows of each half
+// (the form dim = 64 always had). A 4-bit mask on a 24-piece row maps pieces 16..23 to positions
+// 24..31, outside the row (for row 15 past the rows area) -- wrong scores at dim = 64 mod 128 > 64.
+constexpr int scan16_sw(int ks, int r) { return (4 * ks) % 16 == 0 ? (r & 15) : ((r >> 1) & 7); }
+constexpr uint32_t scan16_place(int ks, int r, int p) {
+  return (uint32_t)(r * ks * 64 + ((p ^ scan16_sw(ks, r)) * 16));
+}
+// the placement is a bijection of the block's 16 x 4 KS piece slots (none shared, none past the
+// rows area where the inverse norms sit) that keeps every piece in its own row (a ragged block's
+// buffer descriptor ends with its last live row)
+constexpr bool scan16_place_ok(int ks) {
+  bool seen[16 * 4 * 32] = {};
+  for (int r = 0; r < 16; ++r)
+    for (int p = 0; p < 4 * ks; ++p) {
+      const uint32_t o = scan16_place(ks, r, p);
+      if (o % 16 || o / 16 >= (uint32_t)(16 * 4 * ks) || o / (uint32_t)(ks * 64) != (uint32_t)r || seen[o / 16])
+        return false;
+      seen[o / 16] = true;
+    }
+  return true;
+}
 template <int KS, int D>
 __device__ __forceinline__ void scan16_body(const Scan16Args& a) {
   extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -969,6 +1043,7 @@ __device__ __forceinline__ void scan16_body(const Scan16Args& a) {
   constexpr int BLK = 16 * RB + 1024;    // a block's LDS image: 16 rows, then its inverse norms
   constexpr int F0 = 1 + (D - 2) * (KS + 2);
   constexpr int F = F0 > 63 ? 63 : F0;
+  static_assert(KS >= 2 && KS <= 32 && KS % 2 == 0 && scan16_place_ok(KS), "scan16 LDS placement");
   // lane: row rr of a 16-row block (B port / C column), query group g: queries 4 g .. 4 g + 3
   // (C rows); on the A port the lane carries query rr
   const int lane = threadIdx.x & 63, g = lane >> 4, rr = lane & 15;
@@ -1005,8 +1080,6 @@ __device__ __forceinline__ void scan16_body(const Scan16Args& a) {
     return;
   }
   uint8_t* ring = smem + wid * D * BLK;
-  // chunk swizzle: 16 consecutive rows at one chunk position land on 16 distinct bank quads
-  auto sw = [](int r) { return RB >= 256 ? (r & 15) : ((r >> 1) & 7); };
   u32x4 qf[KS];   // A port: query rr, dims (4 s + g) * 8 .. + 7
   {
     const u16* qp = a.q16 + (int64_t)min(rr, a.nq - 1) * (KS * 32) + g * 8;
@@ -1020,12 +1093,12 @@ __device__ __forceinline__ void scan16_body(const Scan16Args& a) {
 #pragma unroll
   for (int t = 0; t < KS; ++t) {
     const int o = t * 1024 + lane * 16, r = o / RB, p = (o % RB) / 16;
-    doff[t] = (uint32_t)(r * RB + ((p ^ sw(r)) * 16));
+    doff[t] = scan16_place(KS, r, p);
   }
   const uint32_t ioff = lane < 4 ? (uint32_t)lane * 16 : BUF_OOB;
   uint32_t foff[KS];   // B port: row rr of the block, chunk 4 s + g
 #pragma unroll
-  for (int s = 0; s < KS; ++s) foff[s] = (uint32_t)(rr * RB + (((4 * s + g) ^ sw(rr)) * 16));
+  for (int s = 0; s < KS; ++s) foff[s] = scan16_place(KS, rr, 4 * s + g);
   auto row0_of = [&](int64_t i) { return (w + (i >> 4) * W) * SCAN_CHUNK + (i & 15) * 16; };
   auto issue = [&](int64_t i, int buf) {
     const int64_t r0 = row0_of(i);
@@ -1141,7 +1214,8 @@ __global__ __launch_bounds__(256) void collect_ge_kernel(const float* S, int lq,
       float tq = t[0];
 #pragma unroll
       for (int j = 1; j < 16; ++j) tq = q == j ? t[j] : tq;
-      if (v[u] >= tq && q < nq) {
+      // (e < total: the -inf pads of a partial last group are no rows, even at th = -inf)
+      if (v[u] >= tq && q < nq && e < (C << lq)) {
         const int slot = atomicAdd(cnt + q, 1);
         if (slot < cap) {
           cs[(int64_t)q * cap + slot] = v[u];

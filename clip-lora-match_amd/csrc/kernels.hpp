@@ -179,8 +179,8 @@ hipError_t topk_rows(const float* scores, int64_t lds, int64_t nq, int64_t C, in
                      int64_t base, float* out_s, int64_t* out_i, int64_t ldo, hipStream_t s);
 // top-k of any k (k > 1024, or candidate lists longer than one LDS sort): exact k-th key by radix
 // select, the k composites collected, sorted (LDS runs + merge passes), emitted. idx == null: the
-// global index of column j is base + j; else idx[row * ldi + j] (< 0: an empty slot, never taken
-// before a score). Rows with fewer than k entries end in (-inf, -1). nq <= 65535; ws of
+// global index of column j is base + j (any base); else idx[row * ldi + j] (< 0: an empty slot, never
+// taken before a score; the values must be below 2^32: ties are ordered by their low 32 bits). Rows with fewer than k entries end in (-inf, -1). nq <= 65535; ws of
 // topk_any_ws_bytes(nq, k) device bytes.
 size_t topk_any_ws_bytes(int64_t nq, int k);
 hipError_t topk_any(const float* scores, int64_t lds, const int64_t* idx, int64_t ldi, int64_t nq, int64_t C, int k,
@@ -191,9 +191,12 @@ hipError_t count_ge(const float* scores, int64_t lds, int64_t nq, int64_t C, con
 hipError_t count_ge16(const u16* scores, int64_t lds, int64_t nq, int64_t C, const float* th, int* cnt, hipStream_t s);
 hipError_t kth_thresholds16(const u16* scores, int64_t lds, int64_t nq, int64_t C, int k, float margin, float* th,
                             hipStream_t s);
-// merge `parts` candidate lists per row: in [nq, parts*k_in] -> out [nq, k]
+// merge `parts` candidate lists per row: in [nq, parts*k_in] -> out [nq, k] by (score desc, index
+// asc); indices are any int64 >= 0 (< 0: an empty slot)
 hipError_t topk_merge(const float* in_s, const int64_t* in_i, int64_t nq, int parts, int k_in,
                       int k, float* out_s, int64_t* out_i, hipStream_t s);
+// out[0] (device) = the largest index of idx[0, n), 0 if none is >= 0
+hipError_t max_index(const int64_t* idx, int64_t n, int64_t* out, hipStream_t s);
 hipError_t l2_normalize_rows(float* rows, int64_t n, int dim, hipStream_t s);
 hipError_t fuse_rows(const float* a, float wa, const float* b, float wb, int64_t n, int dim, float* out,
                      hipStream_t s);

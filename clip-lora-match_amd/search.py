@@ -337,8 +337,10 @@ class TextSearchIndex:
         scores, indices = self.search_batch(query_emb, top_k)
         results: List[SearchResult] = []
         for idx, score in zip(indices[0].tolist(), scores[0].tolist()):
-            img = self.image_paths[idx] if idx < len(self.image_paths) else ""
-            txt = self.texts[idx] if idx < len(self.texts) else ""
+            # an index outside [0, len) has no metadata: the (-inf, -1) pad of a short result must
+            # not read the last item's through Python's negative indexing
+            img = self.image_paths[idx] if 0 <= idx < len(self.image_paths) else ""
+            txt = self.texts[idx] if 0 <= idx < len(self.texts) else ""
             results.append(SearchResult(index=idx, score=float(score), image_path=img, text=txt))
         return results
 

@@ -163,7 +163,9 @@ int clm_index_destroy(clm_index* idx);
 int clm_index_append(clm_index* idx, const void* rows, int dtype, int64_t n, void* stream);
 int64_t clm_index_size(const clm_index* idx);
 int clm_index_reset(clm_index* idx);
-/* index of row 0 in the global (all-shard) numbering, for multi-GPU shards */
+/* index of row 0 in the global (all-shard) numbering, for multi-GPU shards: any value in
+ * [0, 2^62] (one index holds fewer than 2^32 rows; its searches order equal scores by the local
+ * row, so results are the offset-0 results plus the offset) */
 int clm_index_set_offset(clm_index* idx, int64_t global_offset);
 /* copy rows [start, start+n) back as fp32 (host or device dst) */
 int clm_index_read(clm_index* idx, int64_t start, int64_t n, float* dst, void* stream);
@@ -204,7 +206,9 @@ int clm_cosine_scores(int hip_device, const float* q, int64_t nq, const float* c
                       int dim, float* out, void* stream);
 
 /* merge `parts` sorted candidate lists per query: scores/idx [nq, parts*k_in]
- * -> [nq, k] by (score desc, index asc) */
+ * -> [nq, k] by (score desc, index asc); idx < 0 marks an empty slot. Indices are any int64 >= 0
+ * while parts * k_in <= 8192 and k <= 1024 (one LDS sort per query); larger merges take indices
+ * below 2^32 and return CLM_E_ARG for any other. */
 int clm_topk_merge(int hip_device, const float* scores, const int64_t* idx, int64_t nq,
                    int parts, int k_in, int k, float* out_scores, int64_t* out_idx, void* stream);
 
@@ -246,6 +250,23 @@ void clm_debug_set(int flags);
  * general path, k <= 1024); both give the same bits. */
 int clm_topk_threshold(int hip_device, const float* scores, int64_t lds, int64_t nq, int64_t C, int k,
                        float margin, int method, float* th, void* stream);
+/* the small-batch search's streaming scan (nq <= 16 fp16 queries q16 [nq, dim] against fp16 rows16
+ * [N, dim], device pointers): out [N, ldo] f32 = acc * qinv[q] * inv[row], query q of a row in
+ * column q (ldo = 1, 2, 4, 8 or 16, >= nq; columns of a group of four that starts at or past nq
+ * are not written), cmax [nq, ceil(N / 256)] = each 256-row chunk's largest score (NaN ignored),
+ * wtop (or NULL) [nq, ldw] = every wave's 8 largest chunk maxima at columns 8 w .. 8 w + 7 (-inf
+ * padded), ldw >= 8 * clm_scan16_waves(N, dim). dim % 64 == 0 in [64, 1024]; else CLM_E_ARG.
+ * The extents are the caller's to provide: out holds N * ldo floats, cmax nq * ceil(N / 256),
+ * wtop nq * ldw. clm_scan16_waves means something only for a dim that clm_scan16 accepts. */
+int clm_scan16(int hip_device, const uint16_t* rows16, const float* inv, int64_t N, int dim, const uint16_t* q16,
+               const float* qinv, int nq, float* out, int64_t ldo, float* cmax, float* wtop, int64_t ldw,
+               void* stream);
+int64_t clm_scan16_waves(int hip_device, int64_t N, int dim);
+/* ... and its candidate collection: every (score, base + row) of column q of scores [C, ldq]
+ * (ldq a power of two in [nq, 16]) with score >= th[q] appended to q's list cand_s / cand_i
+ * [nq, cap] in no fixed order; cnt[q] (zeroed by the caller) counts them all, stored or not. */
+int clm_collect_ge(int hip_device, const float* scores, int ldq, int nq, int64_t C, const float* th, int* cnt, int cap,
+                   float* cand_s, int64_t* cand_i, int64_t base, void* stream);
 /* attention over qkv [B*T, 3*H*64] (q pre-scaled by 64^-1/2), out [B*T, ldo] (device
  * pointers); causal: 0 / non-0 switch (the text tower's mask). */
 int clm_attention(int hip_device, int dtype, int causal, const void* qkv, void* out, int64_t ldo,

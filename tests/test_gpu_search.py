@@ -744,6 +744,51 @@ def test_merge_past_one_sort():
         assert np.array_equal(i[q], ix[q][ok][order]) and np.array_equal(s[q], sc[q][ok][order])
 
 
+@pytest.mark.parametrize("device_lists", [False, True])
+def test_merge_indices_past_2_32(device_lists):
+    """clm_topk_merge of shard lists whose global indices lie past 2^32 (shards with any offset):
+    the indices come back whole, in (score desc, index asc) order with tied scores across lists
+    whose indices differ only above bit 32 or only below it, empty (-1) slots last, k past the
+    valid entries padded with (-inf, -1). A merge past one LDS sort refuses such indices."""
+    from clip_lora_match_amd import _capi as C
+    g = np.random.default_rng(9)
+    nq, parts, k_in, k = 3, 4, 300, 700
+    n_in = parts * k_in
+    sc = (g.integers(0, 12, (nq, n_in)) / 8.0).astype(np.float32)          # long tie groups
+    offs = np.array([5_000_000_000, 0, (1 << 32) + 7, 1 << 33], dtype=np.int64)
+    ix = np.stack([np.concatenate([o + g.permutation(1000)[:k_in] for o in offs]) for _ in range(nq)])
+    ix[0, : 2 * k_in] = np.concatenate([offs[0] + np.arange(k_in), offs[1] + np.arange(k_in)])
+    sc[0, : 2 * k_in] = 2.0     # one group across two lists: same low words but for list 0's offset
+    ix[1, ::3] = -1
+    ix[2, 5:] = -1              # fewer valid entries than k
+    os_, oi = np.empty((nq, k), np.float32), np.empty((nq, k), np.int64)
+    if device_lists:
+        ds, di = torch.from_numpy(sc).cuda(), torch.from_numpy(ix).cuda()
+        do, dj = torch.empty((nq, k), device="cuda"), torch.empty((nq, k), dtype=torch.int64, device="cuda")
+        C.check(C.lib().clm_topk_merge(0, C.ptr(ds), C.ptr(di), nq, parts, k_in, k, C.ptr(do), C.ptr(dj),
+                                       C.stream_of(ds.device)), "clm_topk_merge")
+        torch.cuda.synchronize()
+        os_, oi = do.cpu().numpy(), dj.cpu().numpy()
+    else:
+        C.check(C.lib().clm_topk_merge(0, sc.ctypes.data, ix.ctypes.data, nq, parts, k_in, k, os_.ctypes.data,
+                                       oi.ctypes.data, None), "clm_topk_merge")
+    for q in range(nq):
+        ok = ix[q] >= 0
+        order = np.lexsort((ix[q][ok], -sc[q][ok]))[:k]
+        m = order.size
+        assert np.array_equal(oi[q, :m], ix[q][ok][order]) and np.array_equal(os_[q, :m], sc[q][ok][order]), q
+        assert (oi[q, m:] == -1).all() and np.isneginf(os_[q, m:]).all()
+    big_s = np.zeros((1, 3 * 3000), np.float32)
+    big_i = np.arange(3 * 3000, dtype=np.int64)[None, :].copy()
+    bo, bi = np.empty((1, 10), np.float32), np.empty((1, 10), np.int64)
+    assert C.lib().clm_topk_merge(0, big_s.ctypes.data, big_i.ctypes.data, 1, 3, 3000, 10, bo.ctypes.data,
+                                  bi.ctypes.data, None) == C.CLM_OK
+    assert np.array_equal(bi[0], np.arange(10))
+    big_i[0, 4000] = 1 << 32
+    assert C.lib().clm_topk_merge(0, big_s.ctypes.data, big_i.ctypes.data, 1, 3, 3000, 10, bo.ctypes.data,
+                                  bi.ctypes.data, None) == C.CLM_E_ARG
+
+
 def test_filter_tile_per_block_near_duplicates(monkeypatch):
     """The filter pass's tile is chosen per query block from that block's sampled candidate counts
     (no state carried between searches): a near-duplicate block runs gemm_kernel 256 x 256, a random
@@ -856,11 +901,14 @@ def test_small_batch_vs_reference_golden(name, nq, monkeypatch):
     assert st["small_scan"] > 0, st
 
 
-@pytest.mark.parametrize("dim,n,fp32_rows", [(512, 1_200_003, True), (768, 300_001, False), (64, 100_000, False)])
+@pytest.mark.parametrize("dim,n,fp32_rows", [(512, 1_200_003, True), (768, 300_001, False), (64, 100_000, False),
+                                             (192, 70_001, False), (320, 70_001, True), (1024, 66_003, False)])
 def test_small_batch_bit_identical_to_full_scan(dim, n, fp32_rows, monkeypatch):
-    """search_small == the full exact scan, indices and scores bit for bit: nq 1 / 5 / 16, k up to
-    100, near-duplicate queries, a ragged last block and chunk (n % 256 != 0), fp32 rows (re-score
-    against the fp32 copy) and fp16-only indexes, row widths 64 / 512 / 768."""
+    """search_small == the full exact scan, indices and scores bit for bit: nq 1 .. 16 (every score
+    stride 1 / 2 / 4 / 8 / 16), k up to 100 (8: the last on the per-wave top-8 lists, 9: the first
+    on the radix select over the chunk maxima), near-duplicate queries, a ragged last block and
+    chunk (n % 256 != 0), fp32 rows (re-score against the fp32 copy) and fp16-only indexes, row
+    widths 64 / 512 / 768 / 1024 and 192 / 320 (dim % 128 == 64: the scan's 3-bit LDS swizzle)."""
     g = torch.Generator(device="cuda").manual_seed(dim + n)
     rows = torch.randn((n, dim), generator=g, device="cuda")
     if not fp32_rows:
@@ -870,8 +918,9 @@ def test_small_batch_bit_identical_to_full_scan(dim, n, fp32_rows, monkeypatch):
     q[4] = rows[n - 1].float()                      # the last (ragged) block's last row
     idx = CosineIndex(dim, capacity=n)
     idx.append(rows)
-    for nq in (1, 5, 16):
-        for k in (1, 5, 12, 100):
+    nqs, ks = (1, 3, 4, 5, 9, 16), (1, 5, 8, 9, 12, 100)
+    for nq in nqs:
+        for k in ks:
             _set_env(monkeypatch, {"CLM_SEARCH_SMALLQ": "1"})
             s1, i1 = idx.search(q[:nq], k)
             _set_env(monkeypatch, {"CLM_SEARCH_FULL": "1", "CLM_SEARCH_SMALLQ": "0"})
@@ -881,7 +930,122 @@ def test_small_batch_bit_identical_to_full_scan(dim, n, fp32_rows, monkeypatch):
     assert torch.equal(i2[:4, 0], torch.arange(4, device="cuda") * 1000 + 7)
     assert int(i2[4, 0]) == n - 1
     st = idx.stats()
-    assert st["small_scan"] + st["overflow"] == 4 * (1 + 5 + 16) and st["small_scan"] > 0, st
+    assert st["small_scan"] + st["overflow"] == len(ks) * sum(nqs) and st["small_scan"] > 0, st
+    assert st["full_exact"] == len(ks) * sum(nqs), st
+
+
+def _small_vs_full(idx, q, k, monkeypatch):
+    """(scores, indices) of the streaming search, checked bit for bit against the full exact scan"""
+    _set_env(monkeypatch, {"CLM_SEARCH_SMALLQ": "1"})
+    s1, i1 = idx.search(q, k)
+    _set_env(monkeypatch, {"CLM_SEARCH_FULL": "1", "CLM_SEARCH_SMALLQ": "0"})
+    s2, i2 = idx.search(q, k)
+    _set_env(monkeypatch, {})
+    assert torch.equal(i1, i2) and torch.equal(s1.view(torch.int32), s2.view(torch.int32)), (q.shape[0], k)
+    return s1, i1
+
+
+@pytest.mark.parametrize("nq", [1, 4])
+@pytest.mark.parametrize("n,k", [(256 * 40 - 3, 40), (256 * 1024 + 1, 1024)])
+def test_small_batch_k_equals_chunk_count(n, k, nq, monkeypatch):
+    """k as large as the streaming search takes it (k <= the number of 256-row chunks): at 40
+    chunks and k = 40 the threshold comes from the smallest chunk maximum; k = 1024 with a last
+    chunk of one row. Bit-identical to the full exact scan."""
+    dim = 64
+    g = torch.Generator(device="cuda").manual_seed(n + k)
+    rows = torch.randn((n, dim), generator=g, device="cuda").half()
+    q = torch.randn((nq, dim), generator=g, device="cuda")
+    q[0] = rows[n - 1].float() + 0.05 * q[0]
+    idx = CosineIndex(dim, capacity=n)
+    idx.append(rows)
+    _, i1 = _small_vs_full(idx, q, k, monkeypatch)
+    assert int(i1[0, 0]) == n - 1
+    st = idx.stats()
+    assert st["small_scan"] + st["overflow"] == nq and st["full_exact"] == nq, st
+
+
+def test_small_batch_sharded_offset(monkeypatch):
+    """A shard of a row-sharded index (set_offset != 0, here past 2^32) asked a small batch: the
+    streaming search returns the offset-0 full scan's indices plus the offset and the same score
+    bits -- through collect_ge's base and rescore_select's offset on 100,000 rows, and through the
+    whole-list overflow pass (filter GEMM base, rescore_wide, merge) on an index where 2,100 near
+    copies of one row, just past the list capacity of 2,048, all fall inside one query's window."""
+    off = 5_000_000_000
+    g = torch.Generator(device="cuda").manual_seed(11)
+    cases = []
+    rows = torch.randn((100_000, 256), generator=g, device="cuda")
+    q = torch.randn((5, 256), generator=g, device="cuda")
+    q[1] = rows[99_999] + 0.01 * q[1]
+    cases.append((rows, q, (1, 8, 12), False))
+    rows = torch.randn((8_448, 512), generator=g, device="cuda")
+    center = rows[122].clone()
+    dup = torch.arange(2100, device="cuda") * 4 + 3
+    rows[dup] = center + 1e-3 * torch.randn((2100, 512), generator=g, device="cuda")
+    cases.append((rows, torch.stack([center, torch.randn(512, generator=g, device="cuda")]), (1, 5, 20), True))
+    for rows, q, ks, overflows in cases:
+        n = rows.shape[0]
+        idx = CosineIndex(rows.shape[1], capacity=n)
+        idx.append(rows)
+        for k in ks:
+            idx.set_offset(0)
+            _set_env(monkeypatch, {"CLM_SEARCH_FULL": "1", "CLM_SEARCH_SMALLQ": "0"})
+            s0, i0 = idx.search(q, k)
+            assert int(i0.min()) >= 0 and int(i0.max()) < n
+            idx.set_offset(off)
+            s2, i2 = idx.search(q, k)                      # the exact scan on the shard
+            _set_env(monkeypatch, {"CLM_SEARCH_SMALLQ": "1"})
+            s1, i1 = idx.search(q, k)
+            _set_env(monkeypatch, {})
+            bits = s0.view(torch.int32)
+            assert torch.equal(i1, i0 + off) and torch.equal(s1.view(torch.int32), bits), k
+            assert torch.equal(i2, i0 + off) and torch.equal(s2.view(torch.int32), bits), k
+        st = idx.stats()
+        assert st["small_scan"] + st["overflow"] == len(ks) * q.shape[0], st
+        assert (st["overflow"] > 0) == overflows, st
+
+
+@pytest.mark.parametrize("fp32_rows", [True, False])
+def test_small_batch_degenerate_queries_and_rows(fp32_rows, monkeypatch):
+    """A zero query (every score NaN) in a small batch, and an index that holds an all-zero row and
+    a duplicated row: the result is the full exact scan's for every query (indices equal, scores
+    equal as bit patterns), the ordinary queries are unaffected by the zero one, and every
+    returned index is a row of the index -- never the (-inf, -1) pad. The zero query leaves the
+    streaming pass without candidates and is handed to the exact scan (counted there)."""
+    dim, n = 512, 70_001
+    g = torch.Generator(device="cuda").manual_seed(21)
+    rows = torch.randn((n, dim), generator=g, device="cuda")
+    if not fp32_rows:
+        rows = rows.half()
+    q = torch.randn((5, dim), generator=g, device="cuda")
+    q[0] = rows[n - 1].float() + 0.01 * q[0]
+    q[2] = 0
+    plain = [0, 1, 3, 4]
+    idx = CosineIndex(dim, capacity=n)
+    idx.append(rows)
+    for k in (1, 5, 12):
+        s1, i1 = _small_vs_full(idx, q, k, monkeypatch)
+        assert int(i1.min()) >= 0 and int(i1.max()) < n
+        assert int(i1[0, 0]) == n - 1
+        _set_env(monkeypatch, {"CLM_SEARCH_SMALLQ": "1"})
+        sp, ip = idx.search(q[plain], k)
+        _set_env(monkeypatch, {})
+        assert torch.equal(ip, i1[plain]) and torch.equal(sp, s1[plain]), k
+    st = idx.stats()   # per k: 4 + 4 streamed, the zero query and the forced full scan's 5 exact
+    assert st["small_scan"] == 3 * 8 and st["full_exact"] == 3 * 6 and st["overflow"] == 0, st
+    idx.close()
+    rows[1234] = 0
+    rows[40_000] = rows[17]
+    idx = CosineIndex(dim, capacity=n)
+    idx.append(rows)
+    q[1] = rows[17].float()
+    for k in (1, 5, 12):
+        s1, i1 = _small_vs_full(idx, q, k, monkeypatch)
+        assert int(i1.min()) >= 0 and int(i1.max()) < n
+        if k >= 5:   # the duplicated row: equal scores, the smaller index first
+            hit = i1[1].tolist()
+            assert 17 in hit and 40_000 in hit and hit.index(17) + 1 == hit.index(40_000), hit
+    st = idx.stats()
+    assert st["small_scan"] == 3 * 4 and st["full_exact"] == 3 * 6 and st["overflow"] == 0, st
 
 
 def test_small_batch_overflow_near_duplicates(monkeypatch):

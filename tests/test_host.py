@@ -198,3 +198,17 @@ def test_sampled_threshold_stays_a_lower_bound():
             kth_grp = np.sort(grp)[-k]
             assert kth_grp <= kth32
             assert kth32 - kth_grp < 0.05   # and it stays close (more candidates, not a collapse)
+
+
+def test_search_with_embedding_pad_index_has_no_metadata():
+    """An index outside [0, len) -- the (-inf, -1) pad of a short result, or a row past the
+    metadata lists -- gives empty metadata, never the last item's through negative indexing."""
+    import torch
+    from clip_lora_match_amd.search import TextSearchIndex
+    idx = TextSearchIndex.__new__(TextSearchIndex)
+    idx.dim = 4
+    idx.image_paths, idx.texts = ["a.jpg", "b.jpg", "c.jpg"], ["a", "b", "c"]
+    idx.search_batch = lambda q, k: (torch.tensor([[0.9, float("-inf"), 0.1, 0.0]]), torch.tensor([[1, -1, 7, -3]]))
+    res = idx.search_with_embedding(torch.zeros(4), top_k=4)
+    assert [(r.index, r.image_path, r.text) for r in res] == [(1, "b.jpg", "b"), (-1, "", ""), (7, "", ""),
+                                                              (-3, "", "")]
