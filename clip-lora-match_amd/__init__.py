@@ -6,4 +6,15 @@ C-ABI library `libclm.so` (include/clm.h).
 """
 from .config import ModelConfig, TowerConfig, PRESETS, get_preset  # noqa: F401
 
-__all__ = ["ModelConfig", "TowerConfig", "PRESETS", "get_preset"]
+# the retrieval evaluator (evaluate.py), loaded on first use: importing the package stays light
+_EVALUATE = ("retrieval_ranks", "recall_at_k", "mrr", "mean_average_precision", "evaluate_retrieval",
+             "matching_accuracy", "CLIPEvaluator")
+
+__all__ = ["ModelConfig", "TowerConfig", "PRESETS", "get_preset", *_EVALUATE]
+
+
+def __getattr__(name):
+    if name in _EVALUATE:
+        from . import evaluate
+        return getattr(evaluate, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

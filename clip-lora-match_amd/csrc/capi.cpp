@@ -236,7 +236,9 @@ struct clm_index {
   // [3] bounded search with the chunked fp16 scan as step 1
   // [4] / [5]: queries whose filter pass ran on G2 256 x 192 / gemm_kernel 256 x 256 (dense blocks)
   // [6]: queries served by the small-batch streaming search (search_small)
-  int64_t search_stats[7] = {0, 0, 0, 0, 0, 0, 0};
+  // [7] / [8]: rank queries served by the EPI_RANK band pass / by the exact route, [9]: those of [8]
+  // whose band list overflowed its capacity, [10]: band rows re-scored for the queries of [7]
+  int64_t search_stats[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 };
 
 namespace {
@@ -1658,9 +1660,13 @@ static int search_scan_large(clm_index* x, const float* q32, const double* qn, i
 
 // The filter GEMM's cscale bounds (GemmArgs::cbound) for the current rows, computed once per row set
 // on the stream. Null (no skip test) when $CLM_FILTER_SKIP=0 (A/B) or the 8 bytes cannot be had.
+static const unsigned* inv_keys_get(clm_index* x, hipStream_t st);
 static const unsigned* inv_keys_of(clm_index* x, hipStream_t st) {
   static const bool on = !getenv("CLM_FILTER_SKIP") || atoi(getenv("CLM_FILTER_SKIP")) != 0;
-  if (!on) return nullptr;
+  return on ? inv_keys_get(x, st) : nullptr;
+}
+// ... whatever the switch says (the rank router reads them to see a non-finite inverse norm)
+static const unsigned* inv_keys_get(clm_index* x, hipStream_t st) {
   if (!x->inv_keys && hipMalloc(&x->inv_keys, 2 * sizeof(unsigned)) != hipSuccess) {
     (void)hipGetLastError();
     x->inv_keys = nullptr;
@@ -2191,6 +2197,252 @@ int clm_index_search(clm_index* x, const void* q, int q_dtype, int64_t nq, int k
   return CLM_OK;
 }
 
+// ---- exact retrieval ranks (clm_index_rank / clm_index_count_above) ------------------------
+// above(q) = #{rows ahead of the target (t, g) in the search order}. One EPI_RANK pass decides
+// every row whose fp16-pass score s is further than RANK_MARGIN from t: RESCORE_MARGIN's comment
+// bounds |s - exact cosine| by 1.95e-3 + 4.9e-4 = 2.44e-3 for dim <= MARGIN_MAX_DIM, so
+// s > t + 2.5e-3 puts the exact score above t by more than 6e-5 and s < t - 2.5e-3 below it by
+// as much; t's own fp32 rounding and that of t +- margin (6e-8 each) are inside the 6e-5. The
+// comparison is one-sided but only one score of it (s) carries the fp16 error -- t is exact -- so
+// half of RESCORE_MARGIN, which covers two such scores, is enough.
+constexpr float RANK_MARGIN = RESCORE_MARGIN / 2;
+
+// The exact route: exact scores in row windows [nqb, ch] (windowed as search_scan(exact) does:
+// no buffer grows with nq x N) and count_rank per window. q32 / qn / t / g / above: device
+// arrays of the nq queries.
+static int rank_exact(clm_index* x, const float* q32, const double* qn, const float* t, const int64_t* g,
+                      int64_t nq, int64_t* above, hipStream_t st) {
+  const int dim = (int)x->dim;
+  const int64_t N = x->n;
+  const size_t budget = (size_t)512 << 20;
+  const int64_t ch = round_up(std::min<int64_t>(N, 1 << 17), 128);
+  const int64_t nqb = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(nq, 4096), (int64_t)(budget / ((size_t)ch * 4))));
+  int r = grow(&x->ws3, &x->ws3_bytes, (size_t)nqb * ch * 4);
+  if (r) return r;
+  float* sc = (float*)x->ws3;
+  HIPCHK(hipMemsetAsync(above, 0, (size_t)nq * 8, st));
+  for (int64_t q0 = 0; q0 < nq; q0 += nqb) {
+    const int64_t nb = std::min(nqb, nq - q0);
+    for (int64_t r0 = 0; r0 < N; r0 += ch) {
+      const int64_t rn = std::min(ch, N - r0);
+      const void* rp = x->rows32 ? (const void*)(x->rows32 + r0 * dim) : (const void*)(x->rows + r0 * dim);
+      KCHK(exact_scores(q32 + q0 * dim, qn + q0, nb, rp, !x->rows32, rn, dim, sc, ch, st));
+      KCHK(count_rank(sc, ch, nb, rn, x->offset + r0, t + q0, g + q0, above + q0, st));
+    }
+  }
+  return CLM_OK;
+}
+
+// The band route, per block of queries (blocks as search_bounded cuts them): the EPI_RANK GEMM
+// streams the index once (above32 = the rows certainly ahead, the band list = the undecided ones,
+// capacity `cap` per query), rank_rescore settles the band exactly. The band buffer (8 B per
+// slot) stays within $CLM_SEARCH_WS_MB and a quarter of the free HBM: the query block shrinks,
+// the capacity does not. Queries whose band overflowed are appended to `redo`.
+static int rank_band(clm_index* x, const unsigned* keys, const u16* q16, const float* qinv, const float* q32,
+                     const double* qn, const float* t, const int64_t* g, int64_t nq, int64_t cap, int64_t* above,
+                     std::vector<int64_t>& redo, hipStream_t st) {
+  const int dim = (int)x->dim;
+  const int64_t N = x->n;
+  static const int64_t ws_mb = getenv("CLM_SEARCH_WS_MB") ? atoll(getenv("CLM_SEARCH_WS_MB")) : 8192;
+  static const int64_t qb_cap = getenv("CLM_SEARCH_QB") ? std::max<int64_t>(64, atoll(getenv("CLM_SEARCH_QB"))) : 2560;
+  size_t fr = 0, tot = 0;
+  int64_t cap_b = ws_mb << 20;
+  if (hipMemGetInfo(&fr, &tot) == hipSuccess) cap_b = std::min<int64_t>(cap_b, (int64_t)(fr / 4));
+  else (void)hipGetLastError();
+  int64_t nqb = std::min<int64_t>(std::min<int64_t>(nq, qb_cap), std::max<int64_t>(1, cap_b / (cap * 8)));
+  {   // balance: the same number of blocks, equal sizes
+    const int64_t nblk = (nq + nqb - 1) / nqb;
+    const int64_t even = (nq + nblk - 1) / nblk;
+    nqb = std::min<int64_t>(nqb, round_up(even, 64));
+  }
+  size_t off = 0;
+  auto take = [&](size_t bytes) { size_t o = off; off = round_up(off + bytes, 256); return o; };
+  const size_t o_up = take((size_t)nq * 4), o_cnt = take((size_t)nq * 4), o_plan = take((size_t)(nqb + 1) * 4),
+               o_band = take((size_t)nqb * cap * 8);
+  int r = grow(&x->ws2, &x->ws2_bytes, off);
+  if (r) return r;
+  uint8_t* w = (uint8_t*)x->ws2;
+  unsigned* above32 = (unsigned*)(w + o_up);
+  int* cnt = (int*)(w + o_cnt);
+  int64_t* band = (int64_t*)(w + o_band);
+  const void* xrows = x->rows32 ? (const void*)x->rows32 : (const void*)x->rows;
+  HIPCHK(hipMemsetAsync(above32, 0, (size_t)nq * 4, st));
+  HIPCHK(hipMemsetAsync(cnt, 0, (size_t)nq * 4, st));
+  HIPCHK(hipMemsetAsync(above, 0, (size_t)nq * 8, st));   // rank_rescore adds into it
+  for (int64_t q0 = 0; q0 < nq; q0 += nqb) {
+    const int64_t nb = std::min(nqb, nq - q0);
+    GemmArgs gr{};
+    gr.A = q16 + q0 * dim; gr.lda = dim; gr.W = x->rows; gr.ldw = dim;
+    gr.M = (int)nb; gr.N = (int)N; gr.K = dim;
+    gr.rscale = qinv + q0; gr.cscale = x->inv;
+    gr.theta = t + q0; gr.theta_ld = 1; gr.rank_margin = RANK_MARGIN;
+    gr.above = above32 + q0; gr.cnt = cnt + q0; gr.cand_i = band; gr.cap = (int)cap; gr.base = x->offset;
+    gr.m_fastest = 1;
+    gr.cbound = keys;
+    KCHK(gemm_cfg(false, EPI_RANK, -1, gr, st));
+    KCHK(rank_rescore(band, cnt + q0, cap, above32 + q0, q32 + q0 * dim, qn + q0, dim, xrows, !x->rows32, x->offset,
+                      t + q0, g + q0, nb, (int*)(w + o_plan), above + q0, st));
+  }
+  std::vector<int> hcnt(nq);
+  HIPCHK(hipMemcpyAsync(hcnt.data(), cnt, (size_t)nq * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  for (int64_t i = 0; i < nq; ++i) {
+    if (hcnt[i] > cap) redo.push_back(i);
+    else x->search_stats[10] += hcnt[i];
+  }
+  return CLM_OK;
+}
+
+// Router of both entry points. tgt: the targets (rank: global row ids, validated; count_above: the
+// tie-break ids g, any value); t_in: the target scores (count_above) or null (rank: computed here).
+// A query takes the exact route when its band list overflowed or its t is NaN / infinite; the whole
+// call does when the index holds a non-finite inverse norm (a zero row scores NaN in the fp16 pass
+// as in the exact one, but only the latter is compared as the order defines), dim > MARGIN_MAX_DIM,
+// CLM_RANK_EXACT / $CLM_SEARCH_FULL=1 ask for it, or nq x N is at most the 2^24 dot products below
+// which clm_index_search takes its exact scan too (CLM_RANK_BAND / $CLM_SEARCH_BOUNDED=1: the band
+// route at any size, tests). The counts do not depend on the route: both compare exact_cos scores.
+static int rank_run(clm_index* x, const void* q, int q_dtype, int64_t nq, const float* t_in, const int64_t* tgt,
+                    int64_t* out_i, float* out_s, int band_cap, void* stream) {
+  const bool is_rank = t_in == nullptr;
+  if (q_dtype != CLM_F32 && q_dtype != CLM_F16) return fail(CLM_E_ARG, "queries must be f32 or f16");
+  if (x->n == 0) return fail(CLM_E_ARG, "the index is empty");
+  if (nq == 0) return CLM_OK;
+  DeviceGuard guard(x->dev);
+  hipStream_t st = (hipStream_t)stream;
+  const int dim = (int)x->dim;
+  const int64_t N = x->n;
+  std::vector<int64_t> htgt(nq);
+  if (is_device_ptr(tgt)) {
+    HIPCHK(hipMemcpyAsync(htgt.data(), tgt, (size_t)nq * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+  } else {
+    std::memcpy(htgt.data(), tgt, (size_t)nq * 8);
+  }
+  if (is_rank)
+    for (int64_t i = 0; i < nq; ++i)
+      if (htgt[i] < x->offset || htgt[i] - x->offset >= N)
+        return fail(CLM_E_ARG, "target " + std::to_string(htgt[i]) + " of query " + std::to_string(i) +
+                                   " is outside the index [" + std::to_string(x->offset) + ", " +
+                                   std::to_string(x->offset + N) + ")");
+  const bool q_dev = is_device_ptr(q);
+  const size_t q_src_bytes = (size_t)nq * dim * (q_dtype == CLM_F32 ? 4 : 2);
+  size_t off = 0;
+  auto take = [&](size_t bytes) { size_t o = off; off = round_up(off + bytes, 256); return o; };
+  const size_t o_qsrc = q_dev ? 0 : take(q_src_bytes);
+  const size_t o_q16 = take((size_t)nq * dim * 2);
+  const size_t o_qinv = take((size_t)nq * 4);
+  const size_t o_q32 = (q_dtype == CLM_F32 && q_dev) ? 0 : take((size_t)nq * dim * 4);
+  const size_t o_qn = take((size_t)nq * 8);
+  const size_t o_t = take((size_t)nq * 4), o_g = take((size_t)nq * 8), o_ab = take((size_t)nq * 8),
+               o_rk = take((size_t)nq * 8);
+  int r = grow(&x->ws, &x->ws_bytes, off);
+  if (r) return r;
+  uint8_t* ws = (uint8_t*)x->ws;
+  const void* qsrc = q;
+  if (!q_dev) {
+    HIPCHK(hipMemcpyAsync(ws + o_qsrc, q, q_src_bytes, hipMemcpyHostToDevice, st));
+    qsrc = ws + o_qsrc;
+  }
+  u16* q16 = (u16*)(ws + o_q16);
+  float* qinv = (float*)(ws + o_qinv);
+  const float* q32 = (const float*)qsrc;
+  if (!(q_dtype == CLM_F32 && q_dev)) {
+    float* t32 = (float*)(ws + o_q32);
+    if (q_dtype == CLM_F32) HIPCHK(hipMemcpyAsync(t32, qsrc, (size_t)nq * dim * 4, hipMemcpyDeviceToDevice, st));
+    else KCHK(f16_to_f32_rows((const u16*)qsrc, nq, dim, t32, st));
+    q32 = t32;
+  }
+  double* qn = (double*)(ws + o_qn);
+  float* t = (float*)(ws + o_t);
+  int64_t* g = (int64_t*)(ws + o_g);
+  int64_t* above = (int64_t*)(ws + o_ab);
+  int64_t* rank = (int64_t*)(ws + o_rk);
+  const void* xrows = x->rows32 ? (const void*)x->rows32 : (const void*)x->rows;
+  KCHK(query_norms(q32, nq, dim, qn, st));
+  HIPCHK(hipMemcpyAsync(g, htgt.data(), (size_t)nq * 8, hipMemcpyHostToDevice, st));
+  if (is_rank) KCHK(target_scores(q32, qn, nq, dim, xrows, !x->rows32, x->offset, g, t, st));
+  else HIPCHK(hipMemcpyAsync(t, t_in, (size_t)nq * 4, is_device_ptr(t_in) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+  std::vector<float> ht(nq);
+  HIPCHK(hipMemcpyAsync(ht.data(), t, (size_t)nq * 4, hipMemcpyDeviceToHost, st));
+  unsigned hkeys[2] = {0, 0};
+  const unsigned* keys = inv_keys_get(x, st);
+  if (keys) HIPCHK(hipMemcpyAsync(hkeys, keys, sizeof(hkeys), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  // every inverse norm finite and positive (NaN fails both tests): 0 is the inverse of an infinite
+  // norm (an fp16 row holding inf), whose fp16-pass score is NaN like a zero row's
+  const bool inv_ok = keys && key_float(hkeys[0]) > 0.f && key_float(hkeys[1]) <= 3.4028235e38f;
+  const int flags = band_cap > 0 ? band_cap & (CLM_RANK_EXACT | CLM_RANK_BAND) : 0;
+  const int64_t cap_user = band_cap > 0 ? band_cap & CLM_RANK_CAP_MASK : 0;
+  const char* e_full = getenv("CLM_SEARCH_FULL");
+  const char* e_bounded = getenv("CLM_SEARCH_BOUNDED");
+  const bool force_exact = (flags & CLM_RANK_EXACT) || (e_full && atoi(e_full));
+  const bool force_band = (flags & CLM_RANK_BAND) || (e_bounded && atoi(e_bounded));
+  const bool all_exact = force_exact || !inv_ok || dim > MARGIN_MAX_DIM || N > 0x7FFFFFFF ||
+                         (!force_band && (double)nq * (double)N <= (double)(1 << 24));
+  if (all_exact) {
+    if ((r = rank_exact(x, q32, qn, t, g, nq, above, st))) return r;
+    x->search_stats[8] += nq;
+  } else {
+    // fp16 operands of the MFMA pass: queries normalised, then rounded
+    KCHK(rows_to_f16(qsrc, q_dtype == CLM_F32 ? 0 : 1, nq, dim, q16, qinv, st, 2));
+    const int64_t cap = cap_user > 0 ? std::min<int64_t>(cap_user, N) : std::min<int64_t>(N, std::max<int64_t>(2048, N / 8));
+    std::vector<int64_t> redo;
+    if ((r = rank_band(x, keys, q16, qinv, q32, qn, t, g, nq, cap, above, redo, st))) return r;
+    x->search_stats[9] += (int64_t)redo.size();
+    std::vector<char> listed(nq, 0);
+    for (int64_t i : redo) listed[i] = 1;
+    for (int64_t i = 0; i < nq; ++i)
+      if (!listed[i] && !(std::fabs(ht[i]) <= 3.4028235e38f)) redo.push_back(i);   // NaN or infinite t
+    x->search_stats[7] += nq - (int64_t)redo.size();
+    x->search_stats[8] += (int64_t)redo.size();
+    if (!redo.empty()) {   // their queries, norms and targets gathered, one exact pass, counts scattered back
+      const int64_t no = (int64_t)redo.size();
+      size_t o2 = 0;
+      auto take2 = [&](size_t bytes) { size_t o = o2; o2 = round_up(o2 + bytes, 256); return o; };
+      const size_t p_x = take2((size_t)no * 8), p_q = take2((size_t)no * dim * 4), p_n = take2((size_t)no * 8),
+                   p_t = take2((size_t)no * 4), p_g = take2((size_t)no * 8), p_a = take2((size_t)no * 8);
+      if ((r = grow(&x->ws4, &x->ws4_bytes, o2))) return r;
+      uint8_t* wo = (uint8_t*)x->ws4;
+      int64_t* gx = (int64_t*)(wo + p_x);
+      HIPCHK(hipMemcpyAsync(gx, redo.data(), (size_t)no * 8, hipMemcpyHostToDevice, st));
+      KCHK(gather_rows(q32, (int64_t)dim * 4, gx, no, (int64_t)dim * 4, wo + p_q, (int64_t)dim * 4, false, st));
+      KCHK(gather_rows(qn, 8, gx, no, 8, wo + p_n, 8, false, st));
+      KCHK(gather_rows(t, 4, gx, no, 4, wo + p_t, 4, false, st));
+      KCHK(gather_rows(g, 8, gx, no, 8, wo + p_g, 8, false, st));
+      r = rank_exact(x, (const float*)(wo + p_q), (const double*)(wo + p_n), (const float*)(wo + p_t),
+                     (const int64_t*)(wo + p_g), no, (int64_t*)(wo + p_a), st);
+      if (r == CLM_OK) {
+        hipError_t e = gather_rows(wo + p_a, 8, gx, no, 8, above, 8, true, st);
+        if (e != hipSuccess) r = fail(CLM_E_HIP, std::string("rank scatter: ") + hipGetErrorString(e));
+      }
+      (void)hipStreamSynchronize(st);   // `redo` (the source of gx) goes out of scope
+      if (r) return r;
+    }
+  }
+  const int64_t* res = above;
+  if (is_rank) {
+    KCHK(rank_from_above(above, nq, rank, st));
+    res = rank;
+  }
+  HIPCHK(hipMemcpyAsync(out_i, res, (size_t)nq * 8, is_device_ptr(out_i) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
+  if (out_s)
+    HIPCHK(hipMemcpyAsync(out_s, t, (size_t)nq * 4, is_device_ptr(out_s) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));   // workspaces are reused by the next call
+  return CLM_OK;
+}
+
+int clm_index_count_above(clm_index* x, const void* q, int q_dtype, int64_t nq, const float* t_score,
+                          const int64_t* t_index, int64_t* out_above, int band_cap, void* stream) {
+  if (!x || nq < 0 || (nq > 0 && (!q || !t_score || !t_index || !out_above))) return fail(CLM_E_ARG, "bad argument");
+  return rank_run(x, q, q_dtype, nq, t_score, t_index, out_above, nullptr, band_cap, stream);
+}
+
+int clm_index_rank(clm_index* x, const void* q, int q_dtype, int64_t nq, const int64_t* target, int64_t* out_rank,
+                   float* out_score, int band_cap, void* stream) {
+  if (!x || nq < 0 || (nq > 0 && (!q || !target || !out_rank))) return fail(CLM_E_ARG, "bad argument");
+  return rank_run(x, q, q_dtype, nq, nullptr, target, out_rank, out_score, band_cap, stream);
+}
+
 int clm_index_stats(const clm_index* x, int64_t* filtered, int64_t* exact, int64_t* overflow) {
   if (!x) return fail(CLM_E_ARG, "null index");
   if (filtered) *filtered = x->search_stats[0];
@@ -2201,9 +2453,10 @@ int clm_index_stats(const clm_index* x, int64_t* filtered, int64_t* exact, int64
 
 int clm_index_stats2(const clm_index* x, int64_t* out, int n) {
   if (!x || !out || n < 0) return fail(CLM_E_ARG, "bad argument");
-  const int64_t v[7] = {x->search_stats[0], x->search_stats[3], x->search_stats[1], x->search_stats[2],
-                        x->search_stats[4], x->search_stats[5], x->search_stats[6]};
-  for (int i = 0; i < n && i < 7; ++i) out[i] = v[i];
+  const int64_t v[11] = {x->search_stats[0], x->search_stats[3], x->search_stats[1], x->search_stats[2],
+                         x->search_stats[4], x->search_stats[5], x->search_stats[6], x->search_stats[7],
+                         x->search_stats[8], x->search_stats[9], x->search_stats[10]};
+  for (int i = 0; i < n && i < 11; ++i) out[i] = v[i];
   return CLM_OK;
 }
 

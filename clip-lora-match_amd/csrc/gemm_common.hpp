@@ -62,7 +62,7 @@ __device__ __forceinline__ void epilogue_scalar(const GemmArgs& g, const f32x4 (
   for (int mb = 0; mb < TM; ++mb) {
     const int m = wrow + mb * 16;
     if (m >= g.M) continue;
-    const float rs = (EPI == EPI_SCORE || EPI == EPI_FILTER) && g.rscale ? g.rscale[m] : 1.f;
+    const float rs = (EPI == EPI_SCORE || EPI == EPI_FILTER || EPI == EPI_RANK) && g.rscale ? g.rscale[m] : 1.f;
     int64_t prow = m;
     const float* aux = nullptr;
     if constexpr (EPI == EPI_PATCH) {
@@ -87,6 +87,16 @@ __device__ __forceinline__ void epilogue_scalar(const GemmArgs& g, const f32x4 (
           const float v = x * rs * (g.cscale ? g.cscale[nj] : 1.f);
           if (g.out16) ((u16*)g.out)[(int64_t)m * g.ldo + nj] = (u16)f16_down(v);
           else ((float*)g.out)[(int64_t)m * g.ldo + nj] = v;
+        }
+        else if constexpr (EPI == EPI_RANK) {
+          const float sc = x * rs * g.cscale[nj];
+          const float t = g.theta[(int64_t)m * g.theta_ld];
+          if (sc > t + g.rank_margin) {
+            atomicAdd(g.above + m, 1u);
+          } else if (sc >= t - g.rank_margin) {
+            const int slot = atomicAdd(g.cnt + m, 1);
+            if (slot < g.cap) g.cand_i[(int64_t)m * g.cap + slot] = g.base + nj;
+          }
         }
         else {
           const float sc = x * rs * g.cscale[nj];
@@ -152,7 +162,7 @@ __device__ __forceinline__ void epilogue(const GemmArgs& g, const f32x4 (&acc)[B
   float4 cv[C::TN];
 #pragma unroll
   for (int nb = 0; nb < C::TN; ++nb) {
-    if constexpr (!HOIST || EPI == EPI_FILTER) break;   // FILTER: loaded after its skip test
+    if constexpr (!HOIST || EPI == EPI_FILTER || EPI == EPI_RANK) break;   // FILTER / RANK: loaded after the skip test
     const int n = wcol + nb * 16;
     if constexpr (EPI == EPI_SCORE || EPI == EPI_FILTER)
       cv[nb] = (g.cscale && n < g.N) ? *(const float4*)(g.cscale + n) : make_float4(1.f, 1.f, 1.f, 1.f);
@@ -279,13 +289,68 @@ __device__ __forceinline__ void epilogue(const GemmArgs& g, const f32x4 (&acc)[B
         }
       }
     }
-  } else {   // EPI_SCORE / EPI_FILTER: score = dot * rscale[m] * cscale[n], in this order
+  } else {   // EPI_SCORE / EPI_FILTER / EPI_RANK: score = dot * rscale[m] * cscale[n], in this order
     float rs[C::TM], th[C::TM];
 #pragma unroll
     for (int mb = 0; mb < C::TM; ++mb) {
       const int m = wrow + mb * 16;
       rs[mb] = (g.rscale && m < g.M) ? g.rscale[m] : 1.f;
-      if constexpr (EPI == EPI_FILTER) th[mb] = m < g.M ? g.theta[(int64_t)m * g.theta_ld] : 0.f;
+      if constexpr (EPI == EPI_FILTER || EPI == EPI_RANK) th[mb] = m < g.M ? g.theta[(int64_t)m * g.theta_ld] : 0.f;
+    }
+    if constexpr (EPI == EPI_RANK) {
+      // Counting epilogue: th = the row's target score t. A score above t + margin is certainly
+      // ahead of the target (counted: per lane, summed over the 4 lanes l, l ^ 16, l ^ 32, l ^ 48
+      // that hold the row, one integer atomicAdd per row and wave -- the total does not depend on
+      // the order); one inside [t - margin, t + margin] is undecided (its index appended to the
+      // row's band list, FILTER's slot scheme); one below is dropped. FILTER's skip test with the
+      // band's lower edge as the threshold: a row block / block whose largest possible score is
+      // below it holds nothing to count or append.
+      float cmin = 0.f, cmax = 0.f;
+      bool cok = false;
+      if (g.cbound) {
+        cmin = key_float(g.cbound[0]);
+        cmax = key_float(g.cbound[1]);
+        cok = cmin >= 0.f && cmax <= 3.4028235e38f;   // NaN fails both
+      }
+#pragma unroll
+      for (int mb = 0; mb < C::TM; ++mb) {
+        const int m = wrow + mb * 16;
+        const bool live = m < g.M;
+        const float lo = th[mb] - g.rank_margin, hi = th[mb] + g.rank_margin;
+        const bool rok = cok && rs[mb] >= 0.f && rs[mb] <= 3.4028235e38f && lo >= -3.4028235e38f;
+        float bmx[C::TN];
+        float mx = -3.4028235e38f;
+#pragma unroll
+        for (int nb = 0; nb < C::TN; ++nb) {
+          bmx[nb] = fmaxf(fmaxf(acc[mb][nb][0], acc[mb][nb][1]), fmaxf(acc[mb][nb][2], acc[mb][nb][3]));
+          mx = fmaxf(mx, bmx[nb]);
+        }
+        auto reach = [&](float v) { return live && (!rok || (v * rs[mb]) * (v >= 0.f ? cmax : cmin) >= lo); };
+        if (!__any(reach(mx))) continue;
+        unsigned up = 0;
+#pragma unroll
+        for (int nb = 0; nb < C::TN; ++nb) {
+          if (!__any(reach(bmx[nb]))) continue;
+          const int n = wcol + nb * 16;
+          if (!live || n >= g.N) continue;
+          const float4 c = g.cscale ? *(const float4*)(g.cscale + n) : make_float4(1.f, 1.f, 1.f, 1.f);
+          const float sc[4] = {acc[mb][nb][0] * rs[mb] * c.x, acc[mb][nb][1] * rs[mb] * c.y,
+                               acc[mb][nb][2] * rs[mb] * c.z, acc[mb][nb][3] * rs[mb] * c.w};
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            if (sc[j] > hi) {
+              ++up;
+            } else if (sc[j] >= lo) {
+              const int slot = atomicAdd(g.cnt + m, 1);
+              if (slot < g.cap) g.cand_i[(int64_t)m * g.cap + slot] = g.base + n + j;
+            }
+          }
+        }
+        up += (unsigned)__shfl_xor((int)up, 16, 64);
+        up += (unsigned)__shfl_xor((int)up, 32, 64);
+        if (lane < 16 && live && up) atomicAdd(g.above + m, up);
+      }
+      return;
     }
     if constexpr (EPI == EPI_SCORE) {
       if constexpr (C::TN == 8) {
@@ -433,12 +498,12 @@ __device__ __forceinline__ void epilogue(const GemmArgs& g, const f32x4 (&acc)[B
 
 // Stores (vector-memory instructions) one tile's epilogue issues per wave at least, on the
 // vector paths; the main loop's counted vmcnt leaves this many in flight after a tile end
-// (a smaller count than actually issued only over-waits). FILTER stores in branches: 0.
+// (a smaller count than actually issued only over-waits). FILTER / RANK store in branches: 0.
 // EPI_SCORE with TN == 8 may run the group-maxima form (GemmArgs::out16 == 2: one 16-B store per
 // row-block, TM in all), so it counts TM.
 template <int EPI, int TM, int TN>
 constexpr int epi_min_stores() {
-  return epi_stores16(EPI) ? TM * TN / 2 : EPI == EPI_FILTER ? 0 : (EPI == EPI_SCORE && TN == 8) ? TM : TM * TN;
+  return epi_stores16(EPI) ? TM * TN / 2 : (EPI == EPI_FILTER || EPI == EPI_RANK) ? 0 : (EPI == EPI_SCORE && TN == 8) ? TM : TM * TN;
 }
 
 }  // namespace gemm_detail

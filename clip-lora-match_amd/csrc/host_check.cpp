@@ -6,7 +6,8 @@
 //  * every run: argument validation of each entry point (null pointers, bad shapes, bad
 //    dtypes), error strings, version / layout queries;
 //  * with a HIP device: the resident-index lifecycle (create, f16 + f32 appends that grow the
-//    capacity, search on the scan and bounded paths, read-back, offset, reset, destroy),
+//    capacity, search on the scan and bounded paths, ranks on every route and their argument
+//    validation, read-back, offset, reset, destroy),
 //    clm_cosine_scores / clm_topk_merge / clm_l2_normalize / clm_fuse_queries on host buffers,
 //    each checked against a scalar host reference.
 // Exit code 0 = all checks passed (the sanitizers abort the process on their own findings).
@@ -75,6 +76,11 @@ static void argument_checks() {
         CLM_E_ARG);   // not device pointers
   CHECK(clm_collect_ge(0, nullptr, 1, -1, 1, nullptr, nullptr, 1, nullptr, nullptr, 0, nullptr) == CLM_E_ARG);
   CHECK(clm_index_set_offset(nullptr, 0) == CLM_E_ARG);
+  // ranks: null index / null pointers
+  float rq[64] = {1.f}, rs[1] = {0.f};
+  int64_t rt[1] = {0}, ro[1] = {0};
+  CHECK(clm_index_rank(nullptr, rq, CLM_F32, 1, rt, ro, rs, 0, nullptr) == CLM_E_ARG);
+  CHECK(clm_index_count_above(nullptr, rq, CLM_F32, 1, rs, rt, ro, 0, nullptr) == CLM_E_ARG);
 }
 
 static double cos64(const float* a, const float* b, int dim) {
@@ -134,11 +140,46 @@ static void device_checks() {
   CHECK(clm_index_set_offset(idx, 1000) == CLM_OK);
   CHECK(clm_index_search(idx, q.data(), CLM_F32, 1, 1, sc.data(), ix.data(), nullptr) == CLM_OK);
   CHECK(ix[0] >= 1000);
+  {   // ranks of global targets on host buffers, every route, against a host count
+    std::vector<int64_t> tg(nq), rk(nq), ab(nq), want(nq);
+    std::vector<float> ts(nq);
+    for (int i = 0; i < nq; ++i) {
+      tg[i] = 1000 + (i * 577) % n;
+      const double t = cos64(&q[(size_t)i * dim], &rows[(size_t)(tg[i] - 1000) * dim], dim);
+      want[i] = 1;
+      for (int j = 0; j < n; ++j) want[i] += cos64(&q[(size_t)i * dim], &rows[(size_t)j * dim], dim) > t;
+    }
+    for (int flag : {0, (int)CLM_RANK_BAND, (int)CLM_RANK_BAND | 4, (int)CLM_RANK_EXACT}) {
+      CHECK(clm_index_rank(idx, q.data(), CLM_F32, nq, tg.data(), rk.data(), ts.data(), flag, nullptr) == CLM_OK);
+      CHECK(clm_index_count_above(idx, q.data(), CLM_F32, nq, ts.data(), tg.data(), ab.data(), flag, nullptr) == CLM_OK);
+      for (int i = 0; i < nq; ++i) CHECK(rk[i] == want[i] && ab[i] == want[i] - 1);
+    }
+    // argument validation: null pointers, a dtype other than f32 / f16, targets outside [offset, offset + n)
+    CHECK(clm_index_rank(idx, nullptr, CLM_F32, nq, tg.data(), rk.data(), ts.data(), 0, nullptr) == CLM_E_ARG);
+    CHECK(clm_index_rank(idx, q.data(), CLM_F32, nq, nullptr, rk.data(), ts.data(), 0, nullptr) == CLM_E_ARG);
+    CHECK(clm_index_rank(idx, q.data(), CLM_F32, nq, tg.data(), nullptr, ts.data(), 0, nullptr) == CLM_E_ARG);
+    CHECK(clm_index_rank(idx, q.data(), CLM_F32, nq, tg.data(), rk.data(), nullptr, 0, nullptr) == CLM_OK);
+    CHECK(clm_index_rank(idx, q.data(), CLM_BF16, nq, tg.data(), rk.data(), ts.data(), 0, nullptr) == CLM_E_ARG);
+    CHECK(clm_index_rank(idx, q.data(), CLM_F32, -1, tg.data(), rk.data(), ts.data(), 0, nullptr) == CLM_E_ARG);
+    CHECK(clm_index_count_above(idx, q.data(), CLM_F32, nq, nullptr, tg.data(), ab.data(), 0, nullptr) == CLM_E_ARG);
+    CHECK(clm_index_count_above(idx, q.data(), CLM_F32, nq, ts.data(), nullptr, ab.data(), 0, nullptr) == CLM_E_ARG);
+    CHECK(clm_index_count_above(idx, q.data(), CLM_F32, nq, ts.data(), tg.data(), nullptr, 0, nullptr) == CLM_E_ARG);
+    for (int64_t bad : {(int64_t)-1, (int64_t)999, (int64_t)1000 + n, (int64_t)1 << 40}) {
+      tg[nq - 1] = bad;
+      CHECK(clm_index_rank(idx, q.data(), CLM_F32, nq, tg.data(), rk.data(), ts.data(), 0, nullptr) == CLM_E_ARG);
+    }
+  }
   int64_t st[4] = {-1, -1, -1, -1};
   CHECK(clm_index_stats2(idx, st, 4) == CLM_OK && st[0] >= 0);
   CHECK(clm_index_reset(idx) == CLM_OK && clm_index_size(idx) == 0);
   CHECK(clm_index_search(idx, q.data(), CLM_F32, nq, 3, sc.data(), ix.data(), nullptr) == CLM_OK);
   CHECK(ix[0] == -1 && std::isinf(sc[0]));   // empty index: (-inf, -1) slots
+  {   // ... which has no ranks
+    int64_t t0 = 1000, r0 = 0;
+    float s0 = 0.f;
+    CHECK(clm_index_rank(idx, q.data(), CLM_F32, 1, &t0, &r0, &s0, 0, nullptr) == CLM_E_ARG);
+    CHECK(clm_index_count_above(idx, q.data(), CLM_F32, 1, &s0, &t0, &r0, 0, nullptr) == CLM_E_ARG);
+  }
   CHECK(clm_index_destroy(idx) == CLM_OK);
 
   // near-duplicate rows: 3000 copies of one row (and 3000 others) overflow the bounded path's

@@ -334,6 +334,8 @@ int pick_config(int epi, int M, int N) {
     const char* e = getenv("CLM_GEMM_CFG");
     forced = e ? atoi(e) : -1;
   }
+  // the rank pass exists on the filter's tiles only (config 1 and G2's 8-11)
+  if (epi == EPI_RANK) return (forced == 1 || (forced >= 8 && forced <= 11)) ? forced : pick_from(MODELS_G2, M, N);
   if (forced >= 0 && forced < NCFG) return forced;
   // the search's filter GEMM (K = 512, no stores): G2's loop, 256 x 192 -- configs[4] search
   // 95.9 k QPS vs 86.4 k with gemm_kernel 256 x 256 (profiles/r04_v7_search_cfg_ab.txt)
@@ -360,6 +362,12 @@ hipError_t dispatch(int epi, int id, const GemmArgs& g, hipStream_t s) {
     case EPI_PATCH: return launch_id<BF, EPI_PATCH>(id, g, s);
     case EPI_SCORE: return launch_id<BF, EPI_SCORE>(id, g, s);
     case EPI_FILTER: return launch_id<BF, EPI_FILTER>(id, g, s);
+    case EPI_RANK:   // fp16, on the tiles the filter pass runs on
+      if constexpr (!BF) {
+        if (id == 1) return launch_cfg<false, EPI_RANK, 256, 256, 4, 2, 2>(g, s);
+        if (id >= 8 && id <= 11) return gemm2_launch(false, EPI_RANK, id, g, s);
+      }
+      return hipErrorInvalidValue;
     default: return hipErrorInvalidValue;
   }
 }

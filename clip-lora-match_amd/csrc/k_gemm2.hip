@@ -227,6 +227,9 @@ hipError_t by_epi(int epi, int id, const GemmArgs& g, hipStream_t s) {
     case EPI_PATCH: return by_id<BF, EPI_PATCH>(id, g, s);
     case EPI_SCORE: return by_id<BF, EPI_SCORE>(id, g, s);
     case EPI_FILTER: return by_id<BF, EPI_FILTER>(id, g, s);
+    case EPI_RANK:
+      if constexpr (!BF) return by_id<false, EPI_RANK>(id, g, s);
+      return hipErrorInvalidValue;
     default: return hipErrorInvalidValue;
   }
 }

@@ -15,6 +15,7 @@
 // topk_merge: sort of parts*k_in candidates per row (chunk / shard merge).
 #include <algorithm>
 
+#include "exact_cos.hpp"
 #include "kernels.hpp"
 
 namespace clm {
@@ -193,33 +194,8 @@ __global__ __launch_bounds__(NT) void topk_rows_kernel(const float* S, int64_t l
 // the caller's own fp32 (or fp16) rows in fp64 -- fp32 x fp32 products are exact in fp64 --
 // and round once to fp32. Every kernel goes through cos_wave, with one fixed element -> lane
 // mapping and reduction order, so a (query, row) pair scores bit-identically on every path.
-template <typename R>
-__device__ __forceinline__ float row_elem(const R* r, int64_t e) {
-  if constexpr (sizeof(R) == 2) return f16_to_f32(r[e]);
-  else return r[e];
-}
-
-// lane-partial fp64 sums over elements e = lane + 64 i, then one xor-tree over the wave
-template <typename R>
-__device__ __forceinline__ void dot_wave(const float* q, const R* r, int dim, int lane, double& dot, double& rr) {
-  double a = 0.0, b = 0.0;
-  for (int e = lane; e < dim; e += 64) {
-    const double rv = (double)row_elem(r, e);
-    a = fma((double)q[e], rv, a);
-    b = fma(rv, rv, b);
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    a += __shfl_xor(a, o, 64);
-    b += __shfl_xor(b, o, 64);
-  }
-  dot = a;
-  rr = b;
-}
-
-__device__ __forceinline__ float cos_from(double dot, double qn, double rr) {
-  return (float)(dot / (qn * sqrt(rr)));
-}
+// (exact_cos.hpp: row_elem, dot_wave, cos_from -- shared with k_rank.hip)
+using namespace exact_cos;
 
 // qn[q] = ||q||_2 in fp64 (same lane mapping as dot_wave)
 __global__ __launch_bounds__(256) void qnorm_kernel(const float* q, int64_t nq, int dim, double* qn) {

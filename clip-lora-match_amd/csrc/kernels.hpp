@@ -15,8 +15,11 @@ enum Epi {
   EPI_RESID = 2,  // outf[m,n] += acc + bias[n]            (fp32 residual stream)
   EPI_PATCH = 3,  // outf[b*(G+1)+1+p, n] = acc + aux[(1+p)*aux_ld + n], m = b*G+p
   EPI_SCORE = 4,  // outf[m,n] = acc * rscale[m] * cscale[n]  (cosine scores)
-  EPI_FILTER = 5   // s = acc*rscale[m]*cscale[n]; if s >= theta[m]: append (s, base+n) to row m's
+  EPI_FILTER = 5,  // s = acc*rscale[m]*cscale[n]; if s >= theta[m]: append (s, base+n) to row m's
                    // candidate list (atomic slot in cnt[m], capacity cap)
+  EPI_RANK = 6     // s as above against the row's target score t = theta[m]: s > t + rank_margin is
+                   // counted into above[m]; otherwise s >= t - rank_margin appends base+n to row m's
+                   // band list cand_i (slot from cnt[m], capacity cap). fp16, configs 1 and 8-11 only
 };
 constexpr bool epi_stores16(int e) { return e == EPI_STORE || e == EPI_GELU; }
 constexpr bool epi_gelu(int e) { return e == EPI_GELU; }
@@ -34,6 +37,8 @@ struct GemmArgs {
   // optional: order keys {min, max} of cscale[0, N) (value_bounds); lets a wave whose largest
   // accumulator cannot reach any of its rows' thresholds skip the per-element filter
   const unsigned* cbound;
+  // EPI_RANK (with theta = the target scores, cnt / cand_i / cap / base / cbound as EPI_FILTER)
+  unsigned* above; float rank_margin;
   int m_fastest;   // tile order: 1 = consecutive workgroups walk M (share one W tile)
   // split-K (gemm_kernel configs only, EPI_SCORE as the fp32 partial store): ksplit > 1 cuts K
   // into ksplit equal slices; slice s of every tile writes out + s * split_stride
@@ -259,6 +264,32 @@ int64_t scan16_waves(int64_t nchunk, int dim);
 // >= nq) at or above th[q] to q's candidate list [cap] (cnt[q] counts them all)
 hipError_t collect_ge(const float* scores, int ldq, int nq, int64_t C, const float* th, int* cnt, int cap, float* cs,
                       int64_t* ci, int64_t base, hipStream_t s);
+
+// ----------------------------------------------------------- rank (k_rank.hip) ---
+// The order of the search, (score desc, index asc) with NaN above every number: is (s, idx)
+// ahead of the target (t, g)?
+__host__ __device__ inline bool rank_ahead(float s, int64_t idx, float t, int64_t g) {
+  const bool sn = s != s, tn = t != t;
+  if (sn || tn) return sn && (!tn || idx < g);
+  return s > t || (s == t && idx < g);
+}
+// t[q] = exact score of (q, row target[q] - offset): the routine of exact_scores / rescore_select
+hipError_t target_scores(const float* q, const double* qn, int64_t nq, int dim, const void* rows, bool rows_f16,
+                         int64_t offset, const int64_t* target, float* t, hipStream_t s);
+// per query: the band list (global indices [nq, cap], cnt[q] entries; cnt[q] > cap marks an
+// incomplete list, left untouched) re-scored exactly; out[q] (zeroed by the caller) += above32[q] +
+// #{listed rows ahead of the target (t[q], g[q])}; plan: nq + 1 device ints of scratch (the work
+// items' prefix sums); nq * ceil(cap / 64) < 2^31
+hipError_t rank_rescore(const int64_t* band, const int* cnt, int64_t cap, const unsigned* above32, const float* q,
+                        const double* qn, int dim, const void* rows, bool rows_f16, int64_t offset, const float* t,
+                        const int64_t* g, int64_t nq, int* plan, int64_t* out, hipStream_t s);
+// the same count over a window of exact scores [nq, C] (row stride lds), column j being the global
+// row base + j: above[q] += #{j : (scores[q, j], base + j) ahead of (t[q], g[q])}
+hipError_t count_rank(const float* scores, int64_t lds, int64_t nq, int64_t C, int64_t base, const float* t,
+                      const int64_t* g, int64_t* above, hipStream_t s);
+// out[q] = in[q] + 1
+hipError_t rank_from_above(const int64_t* above, int64_t nq, int64_t* rank, hipStream_t s);
+
 __host__ __device__ inline unsigned float_key(float f) {
   const unsigned b = __builtin_bit_cast(unsigned, f);
   return (b & 0x80000000u) ? ~b : (b | 0x80000000u);

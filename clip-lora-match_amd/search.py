@@ -110,6 +110,61 @@ class CosineIndex:
                                          C.stream_of(self.device)), "clm_index_search")
         return s, i
 
+    # ------------------------------------------------------------------ ranks --
+    def _queries(self, queries) -> torch.Tensor:
+        q = torch.as_tensor(queries)
+        if q.dim() == 1:
+            q = q.unsqueeze(0)
+        if q.dim() != 2 or q.shape[1] != self.dim:
+            raise ValueError(f"queries must be [nq, {self.dim}], got {tuple(q.shape)}")
+        if q.dtype not in (torch.float32, torch.float16):
+            q = q.float()
+        return _pad_dim(q.to(self.device), self.dim_p).contiguous()
+
+    def rank(self, queries, targets, band_cap: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Exact retrieval rank of each query's target row (a global id, see set_offset) in the whole
+        index: (ranks [nq] i64, scores [nq] f32) on the GPU, rank = 1 + the number of rows ahead of
+        the target in the search order (exact score desc, index asc), score = the target's exact
+        score -- search(q, k)[1][rank - 1] == target for every k >= rank. No score matrix and no
+        sort: one fp16 MFMA pass counts, the rows too close to call are re-scored exactly
+        (clm_index_rank). band_cap: clm.h (0 = default; CLM_RANK_EXACT / CLM_RANK_BAND force a route).
+        ValueError for a target outside the index or an empty index."""
+        q = self._queries(queries)
+        nq = q.shape[0]
+        t = torch.as_tensor(targets).to(device=self.device, dtype=torch.int64).reshape(-1).contiguous()
+        if t.numel() != nq:
+            raise ValueError(f"targets must hold one row id per query ({nq}), got {t.numel()}")
+        ranks = torch.empty((nq,), dtype=torch.int64, device=self.device)
+        scores = torch.empty((nq,), dtype=torch.float32, device=self.device)
+        code = C.CLM_F32 if q.dtype == torch.float32 else C.CLM_F16
+        C.check(C.lib().clm_index_rank(self._h, C.ptr(q), code, nq, C.ptr(t), C.ptr(ranks), C.ptr(scores),
+                                       int(band_cap), C.stream_of(self.device)), "clm_index_rank")
+        return ranks, scores
+
+    def count_above(self, queries, scores, indices, band_cap: int = 0) -> torch.Tensor:
+        """[nq] i64: the rows of THIS index ahead of a target with exact score scores[i] and global id
+        indices[i] (which may belong to another shard) for query i; the counts of row shards add up
+        to the whole index's (clm_index_count_above)."""
+        q = self._queries(queries)
+        nq = q.shape[0]
+        s = torch.as_tensor(scores).to(device=self.device, dtype=torch.float32).reshape(-1).contiguous()
+        g = torch.as_tensor(indices).to(device=self.device, dtype=torch.int64).reshape(-1).contiguous()
+        if s.numel() != nq or g.numel() != nq:
+            raise ValueError(f"scores and indices must hold one entry per query ({nq})")
+        out = torch.empty((nq,), dtype=torch.int64, device=self.device)
+        code = C.CLM_F32 if q.dtype == torch.float32 else C.CLM_F16
+        C.check(C.lib().clm_index_count_above(self._h, C.ptr(q), code, nq, C.ptr(s), C.ptr(g), C.ptr(out),
+                                              int(band_cap), C.stream_of(self.device)), "clm_index_count_above")
+        return out
+
+    def rank_stats(self) -> dict:
+        """rank / count_above queries served by the MFMA band pass (`band`), by the exact route
+        (`exact`), those of the latter whose band list overflowed its capacity (`overflow`), and the
+        band rows the band pass left to the exact re-score (`band_rows`)"""
+        v = (ctypes.c_int64 * 11)()
+        C.check(C.lib().clm_index_stats2(self._h, v, 11))
+        return {"band": v[7], "exact": v[8], "overflow": v[9], "band_rows": v[10]}
+
     # ------------------------------------------------------------ shard file --
     def save_shard(self, path: Union[str, Path], meta: Optional[dict] = None, chunk_rows: int = 1 << 20) -> None:
         """Write the index's internal state (fp16 operands, fp32 inverse norms, the fp32 rows if

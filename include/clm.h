@@ -20,6 +20,9 @@
  *                              (rows re-normalised at load, :68)
  *   clm_index_search           TextSearchIndex.search_with_embedding search.py:70-115,
  *                              top_k_similar src/embedding/similarity.py:36-58
+ *   clm_index_rank,            (new) the rank of each query's ground-truth row in the whole index,
+ *   clm_index_count_above      what scripts/evaluate_model.py:60-103 (compute_recall_at_k / _mrr /
+ *                              _map) reads off argsort positions of a full [nq, N] matrix
  *   clm_cosine_scores          cosine_similarity similarity.py:10-33
  *   clm_topk_merge             (new) merge of per-shard top-k lists for the
  *                              8-GPU sharded search
@@ -189,16 +192,50 @@ int clm_index_import(clm_index* idx, const uint16_t* rows16, const float* inv, c
 int clm_index_search(clm_index* idx, const void* q, int q_dtype, int64_t nq, int k,
                      float* out_scores, int64_t* out_idx, void* stream);
 
+/* Exact retrieval ranks. "Exact score" s_j of row j for query q is the score of clm_index_search:
+ * fp32(cos64(q, row j)) of the rows as the index keeps them (the fp32 rows when it keeps them, else
+ * the fp16 rows), from the device routine every exact score of the library comes from. For a
+ * target with score t (fp32) and global index g (row 0 is index `global_offset`):
+ *
+ *     above(q) = #{ rows j : s_j > t  or  (s_j == t and global_index(j) < g) }
+ *     rank(q)  = 1 + above(q)
+ *
+ * -- the search order (score desc, index asc), so rank == r means that clm_index_search with any
+ * k >= r returns the target at position r - 1. A NaN score sorts above every number (torch.topk's
+ * order, and the exact scan's); NaNs tie with each other and are ordered by index.
+ *
+ * clm_index_count_above is the primitive: out_above[i] = above(q_i) over this index's rows for the
+ * given (t_score[i], t_index[i]); t_index is any int64 (the target may live in another shard: the
+ * counts of row shards add up to the whole index's). clm_index_rank takes target[i], a global id in
+ * [offset, offset + size), computes t as the exact score of (q_i, that row), counts, and writes
+ * out_rank[i] = rank and out_score[i] = t (out_score may be NULL). q [nq, dim] CLM_F32|CLM_F16;
+ * every pointer host or device, as in clm_index_search. One fp16 MFMA pass counts the rows whose
+ * fp16-pass score is clearly above t and lists those within a margin of it (the band), which are
+ * re-scored exactly; no buffer grows with nq x size. band_cap <= 0: the default band capacity per
+ * query, min(size, max(2048, size / 8)); > 0: its low bits (CLM_RANK_CAP_MASK) cap the band list
+ * (0 = default) -- a query whose band is longer is served by the exact route, windows of exact
+ * scores and the same count -- and CLM_RANK_EXACT sends every query that way, CLM_RANK_BAND keeps
+ * the MFMA pass even for problems small enough for the exact route (both for tests: the results do
+ * not depend on the route). CLM_E_ARG: a target outside the index, an empty index, a null pointer,
+ * a dtype other than f32 / f16. */
+enum { CLM_RANK_EXACT = 1 << 30, CLM_RANK_BAND = 1 << 29, CLM_RANK_CAP_MASK = (1 << 29) - 1 };
+int clm_index_count_above(clm_index* idx, const void* q, int q_dtype, int64_t nq, const float* t_score,
+                          const int64_t* t_index, int64_t* out_above, int band_cap, void* stream);
+int clm_index_rank(clm_index* idx, const void* q, int q_dtype, int64_t nq, const int64_t* target,
+                   int64_t* out_rank, float* out_score, int band_cap, void* stream);
+
 /* search-path counters since creation: queries served by the sampled single-pass bounded
  * search (`filtered`), by the exact scan or the fp16-scan-bounded search (`exact`), and
  * bounded queries whose candidate list overflowed (redone by a whole-list pass, or by the exact
  * scan when the list is longer than 8192 / k chunks of 4096) */
 int clm_index_stats(const clm_index* idx, int64_t* filtered, int64_t* exact, int64_t* overflow);
-/* out[0..n), n <= 7: sampled bounded, fp16-scan bounded, full exact scan, overflow re-runs, then the
+/* out[0..n), n <= 11: sampled bounded, fp16-scan bounded, full exact scan, overflow re-runs, then the
  * sampled queries whose filter pass ran on the G2 256 x 192 tiles / on gemm_kernel 256 x 256 (chosen
  * per query block from the block's sampled candidate counts: near-duplicate blocks take the latter),
  * then the queries served by the small-batch streaming search (nq <= 16 on a large index: one pass
- * over the fp16 rows, thresholds from 256-row chunk maxima) */
+ * over the fp16 rows, thresholds from 256-row chunk maxima), then the rank / count_above queries
+ * served by the band pass, by the exact route, those of the latter whose band list overflowed, and
+ * the band rows re-scored for the band-served queries */
 int clm_index_stats2(const clm_index* idx, int64_t* out, int n);
 
 /* full cosine matrix, exact: out [nq, n] f32 = fp32(cos64(q_i, c_j)), any dim */
