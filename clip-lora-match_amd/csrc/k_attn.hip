@@ -473,6 +473,21 @@ __device__ __forceinline__ u32x4 v_frag32v(uint32_t va) {
 __device__ __forceinline__ void lds_wait(u32x4& a, u32x4& b) {
   asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a), "+v"(b));
 }
+// fp32 sum of the eight bf16 values of a packed fragment: four v_dot2 against (1, 1). (Unpacking
+// each word with a shift and a mask and adding in fp32 is 16 instructions for the 4 here; on the
+// L/14 shape attn_long_dma_kernel<true, true> then runs 4 % slower than with the plain fp32 sum
+// of the unrounded P, with this form about 1 %.)
+__device__ __forceinline__ float bf16x8_sum(const u32x4& w) {
+  typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+  const bf16x2 one2 = __builtin_bit_cast(bf16x2, 0x3F803F80u);
+  float s = 0.f;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const uint32_t x = w[i];
+    s = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2, x), one2, s, false);
+  }
+  return s;
+}
 template <int N> struct IC { static constexpr int value = N; };
 
 // T > 128, non-causal (ViT-L/14@336: T = 577), the default form. Same work split and MFMA shapes
@@ -500,7 +515,10 @@ template <int N> struct IC { static constexpr int value = N; };
 // shift m -- kept as a bf16 value -- enters the score accumulator through a fifth MFMA of the QK
 // chain (A = a column of ones, B = -m in k-slot 0): the fast path is then P = exp2(acc), without
 // the 16 v_fma_f32 per 32 keys that apply log2 e and subtract m (one 32-cycle MFMA instead of 64
-// cycles of vector issue).
+// cycles of vector issue). A bf16 shift is up to half a log2-unit off the row's top score, so
+// even that key's P is no power of two and loses bits when it is packed for the PV MFMA: the row
+// sum therefore adds the packed (rounded) P, the very values O accumulates, not the fp32 ones --
+// otherwise O / l carries P's rounding, up to 2^-8 relative, even on a row that sits on one key.
 template <bool BF, bool QL2E>
 __global__ __launch_bounds__(256, 4) void attn_long_dma_kernel(const u16* qkv, int64_t ldq, u16* out, int64_t ldo,
                                                                int T, int d, int H, int nqb) {
@@ -596,9 +614,10 @@ __global__ __launch_bounds__(256, 4) void attn_long_dma_kernel(const u16* qkv, i
 #pragma unroll
       for (int t = 0; t < 8; ++t) {
         p[t] = __builtin_amdgcn_exp2f(QL2E ? sc[8 * hf + t] : fmaf(sc[8 * hf + t], L2E, -m));
-        rs += p[t];
+        if constexpr (!QL2E) rs += p[t];
       }
       pf[hf] = u32x4{pack2<BF>(p[0], p[1]), pack2<BF>(p[2], p[3]), pack2<BF>(p[4], p[5]), pack2<BF>(p[6], p[7])};
+      if constexpr (QL2E) rs += bf16x8_sum(pf[hf]);
     }
     if ((QL2E && first) || __any(!(rs <= RS_MAX))) {
       float tmax = sc[0];
@@ -634,9 +653,10 @@ __global__ __launch_bounds__(256, 4) void attn_long_dma_kernel(const u16* qkv, i
 #pragma unroll
         for (int t = 0; t < 8; ++t) {
           p[t] = __builtin_amdgcn_exp2f(QL2E ? sc[8 * hf + t] - dm : fmaf(sc[8 * hf + t], L2E, -m));
-          rs += p[t];
+          if constexpr (!QL2E) rs += p[t];
         }
         pf[hf] = u32x4{pack2<BF>(p[0], p[1]), pack2<BF>(p[2], p[3]), pack2<BF>(p[4], p[5]), pack2<BF>(p[6], p[7])};
+        if constexpr (QL2E) rs += bf16x8_sum(pf[hf]);
       }
     }
     return rs;
