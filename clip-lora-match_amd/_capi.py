@@ -23,6 +23,7 @@ CLM_COMPUTE_MIXED = 0x12   # bf16 vision tower, fp16 text tower (clm.h)
 CLM_PAIR_GRAPH = 1
 CLM_PAIR_SPLIT_SHIFT = 8
 CLM_RANK_EXACT, CLM_RANK_BAND, CLM_RANK_CAP_MASK = 1 << 30, 1 << 29, (1 << 29) - 1   # band_cap flag bits (clm.h)
+CLM_LSE_EXACT, CLM_LSE_FAST = CLM_RANK_EXACT, CLM_RANK_BAND
 
 
 class TowerDesc(ctypes.Structure):
@@ -85,6 +86,10 @@ def lib():
         "clm_index_count_above": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_int,
                                           c_void_p]),
         "clm_index_rank": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+        "clm_index_lse": (c_int, [c_void_p, c_void_p, c_int, c_int64, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_int,
+                                  c_void_p]),
+        "clm_index_lse64": (c_int, [c_void_p, c_void_p, c_int, c_int64, ctypes.c_double, c_void_p, c_void_p, c_void_p,
+                                    c_void_p]),
         "clm_index_stats": (c_int, [c_void_p, POINTER(c_int64), POINTER(c_int64), POINTER(c_int64)]),
         "clm_index_stats2": (c_int, [c_void_p, POINTER(c_int64), c_int]),
         "clm_cosine_scores": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p]),
@@ -141,6 +146,7 @@ EXPORTED = (
     "clm_model_desc_size", "clm_prof_enable", "clm_prof_read", "clm_gemm", "clm_gemm_num_configs",
     "clm_attention", "clm_attention_ex", "clm_gemm_scores16", "clm_layernorm", "clm_debug_set",
     "clm_scan16", "clm_scan16_waves", "clm_collect_ge", "clm_index_count_above", "clm_index_rank",
+    "clm_index_lse", "clm_index_lse64",
 )
 CLM_EPI_STORE, CLM_EPI_GELU, CLM_EPI_RESID, CLM_EPI_SCORE = 0, 1, 2, 4
 CLM_PROF_GEMM, CLM_PROF_ATTN, CLM_PROF_LN, CLM_PROF_OTHER = 0, 1, 2, 3

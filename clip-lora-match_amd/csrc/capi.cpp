@@ -238,7 +238,9 @@ struct clm_index {
   // [6]: queries served by the small-batch streaming search (search_small)
   // [7] / [8]: rank queries served by the EPI_RANK band pass / by the exact route, [9]: those of [8]
   // whose band list overflowed its capacity, [10]: band rows re-scored for the queries of [7]
-  int64_t search_stats[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  // [11] / [12]: log-sum-exp queries served by the EPI_LSE pass / by the exact route, [13]: queries
+  // whose EPI_LSE band list overflowed its capacity
+  int64_t search_stats[14] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 };
 
 namespace {
@@ -2443,6 +2445,273 @@ int clm_index_rank(clm_index* x, const void* q, int q_dtype, int64_t nq, const i
   return rank_run(x, q, q_dtype, nq, nullptr, target, out_rank, out_score, band_cap, stream);
 }
 
+// ---- streaming log-sum-exp (clm_index_lse) --------------------------------------------------
+// lse(q) = log sum_j exp(scale * s_j) over the exact scores, in fp64. The fast route's certified
+// bound rests on E >= |fp16-pass score - s_j|: RESCORE_MARGIN's comment gives 1.95e-3 + 4.9e-4 for
+// dim <= MARGIN_MAX_DIM against the exact cosine; 1e-6 more covers the fp32 roundings of s_j itself
+// and of the fp16-pass score's two scale products (6e-8 each).
+constexpr double LSE_E = 1.95e-3 + 4.9e-4 + 1e-6;
+
+// The exact route: exact scores in rank_exact's row windows, folded into a running (maximum, sum)
+// per query. A query's result depends on the index alone, not on nq. q32 / qn / lse / err: device
+// arrays of the nq queries (err may be null). f64: the reference route of clm_index_lse64, the same
+// windows of unrounded fp64 cosines; pair[q] (device, or null) takes the cosine of row target[q].
+static int lse_exact(clm_index* x, const float* q32, const double* qn, int64_t nq, double scale, double* lse,
+                     float* err, hipStream_t st, bool f64 = false, const int64_t* target = nullptr,
+                     double* pair = nullptr) {
+  const int dim = (int)x->dim;
+  const int64_t N = x->n;
+  const size_t budget = (size_t)512 << 20, esz = f64 ? 8 : 4;
+  const int64_t ch = round_up(std::min<int64_t>(N, 1 << 17), 128);
+  const int64_t nqb = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(nq, 4096), (int64_t)(budget / ((size_t)ch * esz))));
+  const size_t o_sc = round_up((size_t)nq * sizeof(double2), 256);
+  int r = grow(&x->ws3, &x->ws3_bytes, o_sc + (size_t)nqb * ch * esz);
+  if (r) return r;
+  double2* state = (double2*)x->ws3;
+  void* sc = (uint8_t*)x->ws3 + o_sc;
+  KCHK(lse_fold_init(state, nq, st));
+  for (int64_t q0 = 0; q0 < nq; q0 += nqb) {
+    const int64_t nb = std::min(nqb, nq - q0);
+    for (int64_t r0 = 0; r0 < N; r0 += ch) {
+      const int64_t rn = std::min(ch, N - r0);
+      const void* rp = x->rows32 ? (const void*)(x->rows32 + r0 * dim) : (const void*)(x->rows + r0 * dim);
+      if (f64) {
+        KCHK(lse_scores64(q32 + q0 * dim, qn + q0, nb, rp, !x->rows32, rn, dim, (double*)sc, ch, st));
+        KCHK(lse_fold64((const double*)sc, ch, nb, rn, scale, state + q0, target ? target + q0 : nullptr, x->offset,
+                        r0, pair ? pair + q0 : nullptr, st));
+      } else {
+        KCHK(exact_scores(q32 + q0 * dim, qn + q0, nb, rp, !x->rows32, rn, dim, (float*)sc, ch, st));
+        KCHK(lse_fold((const float*)sc, ch, nb, rn, scale, state + q0, st));
+      }
+    }
+  }
+  KCHK(lse_fold_finish(state, nq, scale, lse, err, st));
+  return CLM_OK;
+}
+
+// The fast route, per block of queries (rank_band's blocks): the EPI_LSE GEMM streams the index
+// once (band list = the rows at or above theta - RANK_MARGIN, slab = the tail partials), then
+// lse_band_scores re-scores the band and lse_finish combines. Band (8 + 4 B per slot) and slab
+// (4 B per slot) stay within $CLM_SEARCH_WS_MB and a quarter of the free HBM: the query block
+// shrinks. redo[q] = 1 (device) marks the queries left to the exact route; `overflowed` counts
+// those whose band exceeded `cap`.
+static int lse_band(clm_index* x, const u16* q16, const float* qinv, const float* q32, const double* qn,
+                    const float* theta, int64_t nq, int64_t cap, double scale, double* lse, float* err, int* redo,
+                    std::vector<int64_t>& redo_list, int64_t& overflowed, hipStream_t st) {
+  const int dim = (int)x->dim;
+  const int64_t N = x->n;
+  static const int64_t ws_mb = getenv("CLM_SEARCH_WS_MB") ? atoll(getenv("CLM_SEARCH_WS_MB")) : 8192;
+  static const int64_t qb_cap = getenv("CLM_SEARCH_QB") ? std::max<int64_t>(64, atoll(getenv("CLM_SEARCH_QB"))) : 2560;
+  size_t fr = 0, tot = 0;
+  int64_t cap_b = ws_mb << 20;
+  if (hipMemGetInfo(&fr, &tot) == hipSuccess) cap_b = std::min<int64_t>(cap_b, (int64_t)(fr / 4));
+  else (void)hipGetLastError();
+  const int64_t slots = lse_slots(N);
+  const int64_t per_q = cap * 12 + slots * 4;
+  int64_t nqb = std::min<int64_t>(std::min<int64_t>(nq, qb_cap), std::max<int64_t>(1, cap_b / per_q));
+  {   // balance: the same number of blocks, equal sizes
+    const int64_t nblk = (nq + nqb - 1) / nqb;
+    const int64_t even = (nq + nblk - 1) / nblk;
+    nqb = std::min<int64_t>(nqb, round_up(even, 64));
+  }
+  size_t off = 0;
+  auto take = [&](size_t bytes) { size_t o = off; off = round_up(off + bytes, 256); return o; };
+  const size_t o_cnt = take((size_t)nq * 4), o_plan = take((size_t)(nqb + 1) * 4),
+               o_band = take((size_t)nqb * cap * 8), o_bs = take((size_t)nqb * cap * 4),
+               o_slab = take((size_t)nqb * slots * 4);
+  int r = grow(&x->ws2, &x->ws2_bytes, off);
+  if (r) return r;
+  uint8_t* w = (uint8_t*)x->ws2;
+  int* cnt = (int*)(w + o_cnt);
+  int64_t* band = (int64_t*)(w + o_band);
+  float* band_s = (float*)(w + o_bs);
+  float* slab = (float*)(w + o_slab);
+  const void* xrows = x->rows32 ? (const void*)x->rows32 : (const void*)x->rows;
+  HIPCHK(hipMemsetAsync(cnt, 0, (size_t)nq * 4, st));
+  HIPCHK(hipMemsetAsync(redo, 0, (size_t)nq * 4, st));
+  for (int64_t q0 = 0; q0 < nq; q0 += nqb) {
+    const int64_t nb = std::min(nqb, nq - q0);
+    HIPCHK(hipMemsetAsync(slab, 0, (size_t)nb * slots * 4, st));   // the slots the chosen tiles do not use
+    GemmArgs gr{};
+    gr.A = q16 + q0 * dim; gr.lda = dim; gr.W = x->rows; gr.ldw = dim;
+    gr.M = (int)nb; gr.N = (int)N; gr.K = dim;
+    gr.rscale = qinv + q0; gr.cscale = x->inv;
+    gr.theta = theta + q0; gr.theta_ld = 1; gr.rank_margin = RANK_MARGIN;
+    gr.cnt = cnt + q0; gr.cand_i = band; gr.cap = (int)cap; gr.base = x->offset;
+    gr.m_fastest = 1;
+    gr.lse_part = slab; gr.lse_ld = slots; gr.lse_c = (float)(scale * 1.4426950408889634);
+    KCHK(gemm_cfg(false, EPI_LSE, -1, gr, st));
+    KCHK(lse_band_scores(band, cnt + q0, cap, q32 + q0 * dim, qn + q0, dim, xrows, !x->rows32, x->offset, nb,
+                         (int*)(w + o_plan), band_s, st));
+    KCHK(lse_finish(band_s, cnt + q0, cap, slab, slots, theta + q0, scale, LSE_E, N, nb, lse + q0, err + q0,
+                    redo + q0, st));
+  }
+  std::vector<int> hcnt(nq), hredo(nq);
+  HIPCHK(hipMemcpyAsync(hcnt.data(), cnt, (size_t)nq * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(hredo.data(), redo, (size_t)nq * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  for (int64_t i = 0; i < nq; ++i) {
+    if (hredo[i]) redo_list.push_back(i);
+    if (hcnt[i] > cap) ++overflowed;
+  }
+  return CLM_OK;
+}
+
+int clm_index_lse(clm_index* x, const void* q, int q_dtype, int64_t nq, double scale, const float* head_floor,
+                  double* out_lse, float* out_err, int band_cap, void* stream) {
+  if (!x || nq < 0 || (nq > 0 && (!q || !out_lse))) return fail(CLM_E_ARG, "bad argument");
+  if (q_dtype != CLM_F32 && q_dtype != CLM_F16) return fail(CLM_E_ARG, "queries must be f32 or f16");
+  if (!(scale > 0.0 && scale <= 1.7976931348623157e308)) return fail(CLM_E_ARG, "scale must be finite and positive");
+  if (x->n == 0) return fail(CLM_E_ARG, "the index is empty");
+  if (nq == 0) return CLM_OK;
+  DeviceGuard guard(x->dev);
+  hipStream_t st = (hipStream_t)stream;
+  const int dim = (int)x->dim;
+  const int64_t N = x->n;
+  const bool q_dev = is_device_ptr(q);
+  const size_t q_src_bytes = (size_t)nq * dim * (q_dtype == CLM_F32 ? 4 : 2);
+  size_t off = 0;
+  auto take = [&](size_t bytes) { size_t o = off; off = round_up(off + bytes, 256); return o; };
+  const size_t o_qsrc = q_dev ? 0 : take(q_src_bytes);
+  const size_t o_q16 = take((size_t)nq * dim * 2);
+  const size_t o_qinv = take((size_t)nq * 4);
+  const size_t o_q32 = (q_dtype == CLM_F32 && q_dev) ? 0 : take((size_t)nq * dim * 4);
+  const size_t o_qn = take((size_t)nq * 8);
+  const size_t o_th = take((size_t)nq * 4), o_lse = take((size_t)nq * 8), o_err = take((size_t)nq * 4),
+               o_redo = take((size_t)nq * 4);
+  int r = grow(&x->ws, &x->ws_bytes, off);
+  if (r) return r;
+  uint8_t* ws = (uint8_t*)x->ws;
+  const void* qsrc = q;
+  if (!q_dev) {
+    HIPCHK(hipMemcpyAsync(ws + o_qsrc, q, q_src_bytes, hipMemcpyHostToDevice, st));
+    qsrc = ws + o_qsrc;
+  }
+  u16* q16 = (u16*)(ws + o_q16);
+  float* qinv = (float*)(ws + o_qinv);
+  const float* q32 = (const float*)qsrc;
+  if (!(q_dtype == CLM_F32 && q_dev)) {
+    float* t32 = (float*)(ws + o_q32);
+    if (q_dtype == CLM_F32) HIPCHK(hipMemcpyAsync(t32, qsrc, (size_t)nq * dim * 4, hipMemcpyDeviceToDevice, st));
+    else KCHK(f16_to_f32_rows((const u16*)qsrc, nq, dim, t32, st));
+    q32 = t32;
+  }
+  double* qn = (double*)(ws + o_qn);
+  float* theta = (float*)(ws + o_th);
+  double* lse = (double*)(ws + o_lse);
+  float* err = (float*)(ws + o_err);
+  int* redo = (int*)(ws + o_redo);
+  KCHK(query_norms(q32, nq, dim, qn, st));
+  unsigned hkeys[2] = {0, 0};
+  const unsigned* keys = inv_keys_get(x, st);
+  if (keys) HIPCHK(hipMemcpyAsync(hkeys, keys, sizeof(hkeys), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  // as rank_run: every inverse norm finite and positive, or the whole call is exact
+  const bool inv_ok = keys && key_float(hkeys[0]) > 0.f && key_float(hkeys[1]) <= 3.4028235e38f;
+  const int flags = band_cap > 0 ? band_cap & (CLM_LSE_EXACT | CLM_LSE_FAST) : 0;
+  const int64_t cap_user = band_cap > 0 ? band_cap & CLM_RANK_CAP_MASK : 0;
+  const char* e_full = getenv("CLM_SEARCH_FULL");
+  const bool force_exact = (flags & CLM_LSE_EXACT) || (e_full && atoi(e_full));
+  const bool force_fast = (flags & CLM_LSE_FAST) != 0;
+  const bool all_exact = force_exact || !inv_ok || dim > MARGIN_MAX_DIM || N > 0x7FFFFFFF || !head_floor ||
+                         (!force_fast && (double)nq * (double)N <= (double)(1 << 24));
+  if (all_exact) {
+    if ((r = lse_exact(x, q32, qn, nq, scale, lse, err, st))) return r;
+    x->search_stats[12] += nq;
+  } else {
+    HIPCHK(hipMemcpyAsync(theta, head_floor, (size_t)nq * 4,
+                          is_device_ptr(head_floor) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+    // fp16 operands of the MFMA pass: queries normalised, then rounded
+    KCHK(rows_to_f16(qsrc, q_dtype == CLM_F32 ? 0 : 1, nq, dim, q16, qinv, st, 2));
+    const int64_t cap = cap_user > 0 ? std::min<int64_t>(cap_user, N) : std::min<int64_t>(N, std::max<int64_t>(2048, N / 8));
+    std::vector<int64_t> todo;
+    int64_t overflowed = 0;
+    if ((r = lse_band(x, q16, qinv, q32, qn, theta, nq, cap, scale, lse, err, redo, todo, overflowed, st))) return r;
+    x->search_stats[13] += overflowed;
+    x->search_stats[11] += nq - (int64_t)todo.size();
+    x->search_stats[12] += (int64_t)todo.size();
+    if (!todo.empty()) {   // their queries and norms gathered, one exact pass, results scattered back
+      const int64_t no = (int64_t)todo.size();
+      size_t o2 = 0;
+      auto take2 = [&](size_t bytes) { size_t o = o2; o2 = round_up(o2 + bytes, 256); return o; };
+      const size_t p_x = take2((size_t)no * 8), p_q = take2((size_t)no * dim * 4), p_n = take2((size_t)no * 8),
+                   p_l = take2((size_t)no * 8), p_e = take2((size_t)no * 4);
+      if ((r = grow(&x->ws4, &x->ws4_bytes, o2))) return r;
+      uint8_t* wo = (uint8_t*)x->ws4;
+      int64_t* gx = (int64_t*)(wo + p_x);
+      HIPCHK(hipMemcpyAsync(gx, todo.data(), (size_t)no * 8, hipMemcpyHostToDevice, st));
+      KCHK(gather_rows(q32, (int64_t)dim * 4, gx, no, (int64_t)dim * 4, wo + p_q, (int64_t)dim * 4, false, st));
+      KCHK(gather_rows(qn, 8, gx, no, 8, wo + p_n, 8, false, st));
+      r = lse_exact(x, (const float*)(wo + p_q), (const double*)(wo + p_n), no, scale, (double*)(wo + p_l),
+                    (float*)(wo + p_e), st);
+      if (r == CLM_OK) {
+        hipError_t e = gather_rows(wo + p_l, 8, gx, no, 8, lse, 8, true, st);
+        if (e == hipSuccess) e = gather_rows(wo + p_e, 4, gx, no, 4, err, 4, true, st);
+        if (e != hipSuccess) r = fail(CLM_E_HIP, std::string("lse scatter: ") + hipGetErrorString(e));
+      }
+      (void)hipStreamSynchronize(st);   // `todo` (the source of gx) goes out of scope
+      if (r) return r;
+    }
+  }
+  HIPCHK(hipMemcpyAsync(out_lse, lse, (size_t)nq * 8, is_device_ptr(out_lse) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
+  if (out_err)
+    HIPCHK(hipMemcpyAsync(out_err, err, (size_t)nq * 4, is_device_ptr(out_err) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));   // workspaces are reused by the next call
+  return CLM_OK;
+}
+
+// The reference route: lse_exact on the unrounded fp64 cosines. Nothing here is rounded to fp32, so
+// a loss built from out_lse and out_pair is the fp64 loss of the same rows to fp64 rounding.
+int clm_index_lse64(clm_index* x, const void* q, int q_dtype, int64_t nq, double scale, const int64_t* target,
+                    double* out_lse, double* out_pair, void* stream) {
+  if (!x || nq < 0 || (nq > 0 && (!q || !out_lse || (out_pair && !target)))) return fail(CLM_E_ARG, "bad argument");
+  if (q_dtype != CLM_F32 && q_dtype != CLM_F16) return fail(CLM_E_ARG, "queries must be f32 or f16");
+  if (!(scale > 0.0 && scale <= 1.7976931348623157e308)) return fail(CLM_E_ARG, "scale must be finite and positive");
+  if (x->n == 0) return fail(CLM_E_ARG, "the index is empty");
+  if (nq == 0) return CLM_OK;
+  DeviceGuard guard(x->dev);
+  hipStream_t st = (hipStream_t)stream;
+  const int dim = (int)x->dim;
+  const bool q_dev = is_device_ptr(q);
+  const size_t q_src_bytes = (size_t)nq * dim * (q_dtype == CLM_F32 ? 4 : 2);
+  size_t off = 0;
+  auto take = [&](size_t bytes) { size_t o = off; off = round_up(off + bytes, 256); return o; };
+  const size_t o_qsrc = q_dev ? 0 : take(q_src_bytes);
+  const size_t o_q32 = q_dtype == CLM_F32 ? 0 : take((size_t)nq * dim * 4);
+  const size_t o_qn = take((size_t)nq * 8), o_lse = take((size_t)nq * 8), o_pair = take((size_t)nq * 8),
+               o_tg = take((size_t)nq * 8);
+  int r = grow(&x->ws, &x->ws_bytes, off);
+  if (r) return r;
+  uint8_t* ws = (uint8_t*)x->ws;
+  const void* qsrc = q;
+  if (!q_dev) {
+    HIPCHK(hipMemcpyAsync(ws + o_qsrc, q, q_src_bytes, hipMemcpyHostToDevice, st));
+    qsrc = ws + o_qsrc;
+  }
+  const float* q32 = (const float*)qsrc;
+  if (q_dtype != CLM_F32) {
+    KCHK(f16_to_f32_rows((const u16*)qsrc, nq, dim, (float*)(ws + o_q32), st));
+    q32 = (const float*)(ws + o_q32);
+  }
+  double* qn = (double*)(ws + o_qn);
+  double* lse = (double*)(ws + o_lse);
+  double* pair = out_pair ? (double*)(ws + o_pair) : nullptr;
+  int64_t* tg = pair ? (int64_t*)(ws + o_tg) : nullptr;
+  if (pair) {
+    HIPCHK(hipMemcpyAsync(tg, target, (size_t)nq * 8,
+                          is_device_ptr(target) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(pair, 0xFF, (size_t)nq * 8, st));   // NaN: a target outside the index keeps it
+  }
+  KCHK(query_norms(q32, nq, dim, qn, st));
+  if ((r = lse_exact(x, q32, qn, nq, scale, lse, nullptr, st, true, tg, pair))) return r;
+  x->search_stats[12] += nq;
+  HIPCHK(hipMemcpyAsync(out_lse, lse, (size_t)nq * 8, is_device_ptr(out_lse) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
+  if (pair)
+    HIPCHK(hipMemcpyAsync(out_pair, pair, (size_t)nq * 8, is_device_ptr(out_pair) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));   // workspaces are reused by the next call
+  return CLM_OK;
+}
+
 int clm_index_stats(const clm_index* x, int64_t* filtered, int64_t* exact, int64_t* overflow) {
   if (!x) return fail(CLM_E_ARG, "null index");
   if (filtered) *filtered = x->search_stats[0];
@@ -2453,10 +2722,11 @@ int clm_index_stats(const clm_index* x, int64_t* filtered, int64_t* exact, int64
 
 int clm_index_stats2(const clm_index* x, int64_t* out, int n) {
   if (!x || !out || n < 0) return fail(CLM_E_ARG, "bad argument");
-  const int64_t v[11] = {x->search_stats[0], x->search_stats[3], x->search_stats[1], x->search_stats[2],
+  const int64_t v[14] = {x->search_stats[0], x->search_stats[3], x->search_stats[1], x->search_stats[2],
                          x->search_stats[4], x->search_stats[5], x->search_stats[6], x->search_stats[7],
-                         x->search_stats[8], x->search_stats[9], x->search_stats[10]};
-  for (int i = 0; i < n && i < 11; ++i) out[i] = v[i];
+                         x->search_stats[8], x->search_stats[9], x->search_stats[10], x->search_stats[11],
+                         x->search_stats[12], x->search_stats[13]};
+  for (int i = 0; i < n && i < 14; ++i) out[i] = v[i];
   return CLM_OK;
 }
 

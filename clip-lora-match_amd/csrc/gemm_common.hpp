@@ -57,12 +57,14 @@ __device__ __forceinline__ void lds_barrier() {
 // ragged-N epilogue (N or ldo not a multiple of 4): element by element, same arithmetic
 // as the vector paths (score = dot * rscale * cscale in that order)
 template <bool BF, int EPI, int TM, int TN>
-__device__ __forceinline__ void epilogue_scalar(const GemmArgs& g, const f32x4 (&acc)[TM][TN], int wrow, int wcol) {
+__device__ __forceinline__ void epilogue_scalar(const GemmArgs& g, const f32x4 (&acc)[TM][TN], int wrow, int wcol,
+                                                int lse_slot = 0) {
 #pragma unroll
   for (int mb = 0; mb < TM; ++mb) {
     const int m = wrow + mb * 16;
     if (m >= g.M) continue;
-    const float rs = (EPI == EPI_SCORE || EPI == EPI_FILTER || EPI == EPI_RANK) && g.rscale ? g.rscale[m] : 1.f;
+    const float rs = (EPI == EPI_SCORE || EPI == EPI_FILTER || EPI == EPI_RANK || EPI == EPI_LSE) && g.rscale ? g.rscale[m] : 1.f;
+    float lse_sum = 0.f;   // EPI_LSE: this lane's tail terms of row m
     int64_t prow = m;
     const float* aux = nullptr;
     if constexpr (EPI == EPI_PATCH) {
@@ -98,6 +100,16 @@ __device__ __forceinline__ void epilogue_scalar(const GemmArgs& g, const f32x4 (
             if (slot < g.cap) g.cand_i[(int64_t)m * g.cap + slot] = g.base + nj;
           }
         }
+        else if constexpr (EPI == EPI_LSE) {   // the vector path's arithmetic, element by element
+          const float sc = x * rs * g.cscale[nj];
+          const float t = g.theta[(int64_t)m * g.theta_ld];
+          if (sc >= t - g.rank_margin) {
+            const int slot = atomicAdd(g.cnt + m, 1);
+            if (slot < g.cap) g.cand_i[(int64_t)m * g.cap + slot] = g.base + nj;
+          } else {
+            lse_sum += __builtin_amdgcn_exp2f((sc - t) * g.lse_c);
+          }
+        }
         else {
           const float sc = x * rs * g.cscale[nj];
           if (sc >= g.theta[(int64_t)m * g.theta_ld]) {
@@ -109,6 +121,11 @@ __device__ __forceinline__ void epilogue_scalar(const GemmArgs& g, const f32x4 (
           }
         }
       }
+    }
+    if constexpr (EPI == EPI_LSE) {   // the 4 lanes of row m are all live here (m depends on lane & 15 only)
+      lse_sum += __shfl_xor(lse_sum, 16, 64);
+      lse_sum += __shfl_xor(lse_sum, 32, 64);
+      if ((threadIdx.x & 63) < 16) g.lse_part[(int64_t)m * g.lse_ld + lse_slot] = lse_sum;
     }
   }
 }
@@ -152,7 +169,8 @@ __device__ __forceinline__ void epilogue(const GemmArgs& g, const f32x4 (&acc)[B
   const int wrow = m0 + wm * (BM / WM) + (lane & 15);
   const int wcol = n0 + wn * (BN / WN) + (lane >> 4) * 4;
   if ((g.N % 4) != 0 || (g.ldo % 4) != 0) {   // ragged N: scalar tail path
-    epilogue_scalar<BF, EPI, C::TM, C::TN>(g, acc, wrow, wcol);
+    if constexpr (EPI == EPI_LSE) epilogue_scalar<BF, EPI, C::TM, C::TN>(g, acc, wrow, wcol, (n0 / BN) * WN + wn);
+    else epilogue_scalar<BF, EPI, C::TM, C::TN>(g, acc, wrow, wcol);
     return;
   }
   // per-column vectors, loaded once per nb (they do not depend on the row); the RESID/PATCH
@@ -162,7 +180,7 @@ __device__ __forceinline__ void epilogue(const GemmArgs& g, const f32x4 (&acc)[B
   float4 cv[C::TN];
 #pragma unroll
   for (int nb = 0; nb < C::TN; ++nb) {
-    if constexpr (!HOIST || EPI == EPI_FILTER || EPI == EPI_RANK) break;   // FILTER / RANK: loaded after the skip test
+    if constexpr (!HOIST || EPI == EPI_FILTER || EPI == EPI_RANK || EPI == EPI_LSE) break;   // FILTER / RANK: loaded after the skip test; LSE: per block
     const int n = wcol + nb * 16;
     if constexpr (EPI == EPI_SCORE || EPI == EPI_FILTER)
       cv[nb] = (g.cscale && n < g.N) ? *(const float4*)(g.cscale + n) : make_float4(1.f, 1.f, 1.f, 1.f);
@@ -289,13 +307,53 @@ __device__ __forceinline__ void epilogue(const GemmArgs& g, const f32x4 (&acc)[B
         }
       }
     }
-  } else {   // EPI_SCORE / EPI_FILTER / EPI_RANK: score = dot * rscale[m] * cscale[n], in this order
+  } else {   // EPI_SCORE / EPI_FILTER / EPI_RANK / EPI_LSE: score = dot * rscale[m] * cscale[n], in this order
     float rs[C::TM], th[C::TM];
 #pragma unroll
     for (int mb = 0; mb < C::TM; ++mb) {
       const int m = wrow + mb * 16;
       rs[mb] = (g.rscale && m < g.M) ? g.rscale[m] : 1.f;
-      if constexpr (EPI == EPI_FILTER || EPI == EPI_RANK) th[mb] = m < g.M ? g.theta[(int64_t)m * g.theta_ld] : 0.f;
+      if constexpr (EPI == EPI_FILTER || EPI == EPI_RANK || EPI == EPI_LSE) th[mb] = m < g.M ? g.theta[(int64_t)m * g.theta_ld] : 0.f;
+    }
+    if constexpr (EPI == EPI_LSE) {
+      // Log-sum-exp epilogue: th = the row's head floor theta. A score at or above theta - margin
+      // is a band row (its index appended to the row's band list, FILTER's slot scheme; the band
+      // kernel re-scores it exactly); every other row is a tail row and adds
+      // exp2((s - theta) * c), c = scale * log2(e), a term below 1: no running maximum. A NaN score
+      // fails the band test and makes the tail NaN. No skip test: every row contributes. The
+      // terms are summed per lane, then over the 4 lanes l, l ^ 16, l ^ 32, l ^ 48 that hold the
+      // row, and lane l < 16 stores the wave's partial of this column tile to its own slot
+      // (column tile, wave column) of the row's slab: every slot of a live row is written exactly
+      // once per pass, in no atomic, so lse_reduce's fixed-order sum is reproducible.
+      const int slot = (n0 / BN) * WN + wn;
+#pragma unroll
+      for (int mb = 0; mb < C::TM; ++mb) {
+        const int m = wrow + mb * 16;
+        const bool live = m < g.M;
+        const float lo = th[mb] - g.rank_margin;
+        float sum = 0.f;
+#pragma unroll
+        for (int nb = 0; nb < C::TN; ++nb) {
+          const int n = wcol + nb * 16;
+          if (!live || n >= g.N) continue;
+          const float4 c = g.cscale ? *(const float4*)(g.cscale + n) : make_float4(1.f, 1.f, 1.f, 1.f);
+          const float sc[4] = {acc[mb][nb][0] * rs[mb] * c.x, acc[mb][nb][1] * rs[mb] * c.y,
+                               acc[mb][nb][2] * rs[mb] * c.z, acc[mb][nb][3] * rs[mb] * c.w};
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            if (sc[j] >= lo) {
+              const int sl = atomicAdd(g.cnt + m, 1);
+              if (sl < g.cap) g.cand_i[(int64_t)m * g.cap + sl] = g.base + n + j;
+            } else {
+              sum += __builtin_amdgcn_exp2f((sc[j] - th[mb]) * g.lse_c);
+            }
+          }
+        }
+        sum += __shfl_xor(sum, 16, 64);
+        sum += __shfl_xor(sum, 32, 64);
+        if (lane < 16 && live) g.lse_part[(int64_t)m * g.lse_ld + slot] = sum;
+      }
+      return;
     }
     if constexpr (EPI == EPI_RANK) {
       // Counting epilogue: th = the row's target score t. A score above t + margin is certainly
@@ -498,12 +556,12 @@ __device__ __forceinline__ void epilogue(const GemmArgs& g, const f32x4 (&acc)[B
 
 // Stores (vector-memory instructions) one tile's epilogue issues per wave at least, on the
 // vector paths; the main loop's counted vmcnt leaves this many in flight after a tile end
-// (a smaller count than actually issued only over-waits). FILTER / RANK store in branches: 0.
+// (a smaller count than actually issued only over-waits). FILTER / RANK / LSE store in branches: 0.
 // EPI_SCORE with TN == 8 may run the group-maxima form (GemmArgs::out16 == 2: one 16-B store per
 // row-block, TM in all), so it counts TM.
 template <int EPI, int TM, int TN>
 constexpr int epi_min_stores() {
-  return epi_stores16(EPI) ? TM * TN / 2 : (EPI == EPI_FILTER || EPI == EPI_RANK) ? 0 : (EPI == EPI_SCORE && TN == 8) ? TM : TM * TN;
+  return epi_stores16(EPI) ? TM * TN / 2 : (EPI == EPI_FILTER || EPI == EPI_RANK || EPI == EPI_LSE) ? 0 : (EPI == EPI_SCORE && TN == 8) ? TM : TM * TN;
 }
 
 }  // namespace gemm_detail

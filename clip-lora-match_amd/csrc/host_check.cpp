@@ -7,7 +7,8 @@
 //    dtypes), error strings, version / layout queries;
 //  * with a HIP device: the resident-index lifecycle (create, f16 + f32 appends that grow the
 //    capacity, search on the scan and bounded paths, ranks on every route and their argument
-//    validation, read-back, offset, reset, destroy),
+//    validation, the log-sum-exp on every route and its argument validation, read-back, offset,
+//    reset, destroy),
 //    clm_cosine_scores / clm_topk_merge / clm_l2_normalize / clm_fuse_queries on host buffers,
 //    each checked against a scalar host reference.
 // Exit code 0 = all checks passed (the sanitizers abort the process on their own findings).
@@ -81,6 +82,11 @@ static void argument_checks() {
   int64_t rt[1] = {0}, ro[1] = {0};
   CHECK(clm_index_rank(nullptr, rq, CLM_F32, 1, rt, ro, rs, 0, nullptr) == CLM_E_ARG);
   CHECK(clm_index_count_above(nullptr, rq, CLM_F32, 1, rs, rt, ro, 0, nullptr) == CLM_E_ARG);
+  // log-sum-exp: null index
+  double rl[1] = {0.0};
+  CHECK(clm_index_lse(nullptr, rq, CLM_F32, 1, 100.0, rs, rl, rs, 0, nullptr) == CLM_E_ARG);
+  CHECK(clm_index_lse(nullptr, rq, CLM_F32, 0, 100.0, nullptr, nullptr, nullptr, 0, nullptr) == CLM_E_ARG);
+  CHECK(clm_index_lse64(nullptr, rq, CLM_F32, 1, 100.0, nullptr, rl, nullptr, nullptr) == CLM_E_ARG);
 }
 
 static double cos64(const float* a, const float* b, int dim) {
@@ -169,9 +175,61 @@ static void device_checks() {
       CHECK(clm_index_rank(idx, q.data(), CLM_F32, nq, tg.data(), rk.data(), ts.data(), 0, nullptr) == CLM_E_ARG);
     }
   }
+  {   // log-sum-exp on host buffers, every route, against a host fp64 sum; then argument validation
+    const double scale = 1.0 / 0.07;
+    std::vector<float> floor_(nq);
+    std::vector<double> want(nq), got(nq);
+    std::vector<float> er(nq);
+    for (int i = 0; i < nq; ++i) {
+      std::vector<float> s(n);
+      for (int j = 0; j < n; ++j) s[j] = (float)cos64(&q[(size_t)i * dim], &rows[(size_t)j * dim], dim);
+      double acc = 0;
+      for (int j = 0; j < n; ++j) acc += std::exp(scale * (double)s[j]);
+      want[i] = std::log(acc);
+      std::nth_element(s.begin(), s.begin() + 15, s.end(), [](float a, float b) { return a > b; });
+      floor_[i] = s[15];   // the 16th best score
+    }
+    for (int flag : {0, (int)CLM_LSE_FAST, (int)CLM_LSE_FAST | 4, (int)CLM_LSE_EXACT}) {
+      CHECK(clm_index_lse(idx, q.data(), CLM_F32, nq, scale, floor_.data(), got.data(), er.data(), flag, nullptr) == CLM_OK);
+      // 1e-6: the host cosines may differ from the library's in their last fp32 bit
+      for (int i = 0; i < nq; ++i) CHECK(std::fabs(got[i] - want[i]) <= (double)er[i] + 1e-6);
+    }
+    CHECK(clm_index_lse(idx, q.data(), CLM_F32, nq, scale, nullptr, got.data(), nullptr, 0, nullptr) == CLM_OK);
+    int64_t ls[14];
+    CHECK(clm_index_stats2(idx, ls, 14) == CLM_OK && ls[11] >= nq && ls[12] >= 3 * nq && ls[13] >= nq);
+    CHECK(clm_index_lse(idx, nullptr, CLM_F32, nq, scale, floor_.data(), got.data(), er.data(), 0, nullptr) == CLM_E_ARG);
+    CHECK(clm_index_lse(idx, q.data(), CLM_F32, nq, scale, floor_.data(), nullptr, er.data(), 0, nullptr) == CLM_E_ARG);
+    CHECK(clm_index_lse(idx, q.data(), CLM_BF16, nq, scale, floor_.data(), got.data(), er.data(), 0, nullptr) == CLM_E_ARG);
+    CHECK(clm_index_lse(idx, q.data(), CLM_F32, -1, scale, floor_.data(), got.data(), er.data(), 0, nullptr) == CLM_E_ARG);
+    for (double bad : {0.0, -1.0, (double)INFINITY, (double)NAN})
+      CHECK(clm_index_lse(idx, q.data(), CLM_F32, nq, bad, floor_.data(), got.data(), er.data(), 0, nullptr) == CLM_E_ARG);
+    {   // the reference route: unrounded cosines, and the pair scores of rows i
+      std::vector<int64_t> tg(nq);
+      std::vector<double> pr(nq);
+      for (int i = 0; i < nq; ++i) tg[i] = 1000 + i % n;   // the offset set above
+      CHECK(clm_index_lse64(idx, q.data(), CLM_F32, nq, scale, tg.data(), got.data(), pr.data(), nullptr) == CLM_OK);
+      for (int i = 0; i < nq; ++i) {
+        double acc = 0;
+        for (int j = 0; j < n; ++j) acc += std::exp(scale * cos64(&q[(size_t)i * dim], &rows[(size_t)j * dim], dim));
+        CHECK(std::fabs(got[i] - std::log(acc)) <= 1e-10);
+        CHECK(std::fabs(pr[i] - cos64(&q[(size_t)i * dim], &rows[(size_t)(tg[i] - 1000) * dim], dim)) <= 1e-12);
+      }
+      tg[0] = 1000 + n;   // a row the index does not hold
+      CHECK(clm_index_lse64(idx, q.data(), CLM_F32, nq, scale, tg.data(), got.data(), pr.data(), nullptr) == CLM_OK);
+      CHECK(std::isnan(pr[0]) && !std::isnan(pr[nq - 1]));
+      CHECK(clm_index_lse64(idx, q.data(), CLM_F32, nq, scale, nullptr, got.data(), nullptr, nullptr) == CLM_OK);
+      CHECK(clm_index_lse64(idx, q.data(), CLM_F32, nq, scale, nullptr, got.data(), pr.data(), nullptr) == CLM_E_ARG);
+      CHECK(clm_index_lse64(idx, nullptr, CLM_F32, nq, scale, nullptr, got.data(), nullptr, nullptr) == CLM_E_ARG);
+      CHECK(clm_index_lse64(idx, q.data(), CLM_F32, nq, scale, nullptr, nullptr, nullptr, nullptr) == CLM_E_ARG);
+      CHECK(clm_index_lse64(idx, q.data(), CLM_BF16, nq, scale, nullptr, got.data(), nullptr, nullptr) == CLM_E_ARG);
+      CHECK(clm_index_lse64(idx, q.data(), CLM_F32, nq, 0.0, nullptr, got.data(), nullptr, nullptr) == CLM_E_ARG);
+    }
+  }
+  double st_lse = 0.0;
   int64_t st[4] = {-1, -1, -1, -1};
   CHECK(clm_index_stats2(idx, st, 4) == CLM_OK && st[0] >= 0);
   CHECK(clm_index_reset(idx) == CLM_OK && clm_index_size(idx) == 0);
+  CHECK(clm_index_lse(idx, q.data(), CLM_F32, 1, 100.0, nullptr, &st_lse, nullptr, 0, nullptr) == CLM_E_ARG);   // empty
   CHECK(clm_index_search(idx, q.data(), CLM_F32, nq, 3, sc.data(), ix.data(), nullptr) == CLM_OK);
   CHECK(ix[0] == -1 && std::isinf(sc[0]));   // empty index: (-inf, -1) slots
   {   // ... which has no ranks

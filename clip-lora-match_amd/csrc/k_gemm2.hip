@@ -230,6 +230,9 @@ hipError_t by_epi(int epi, int id, const GemmArgs& g, hipStream_t s) {
     case EPI_RANK:
       if constexpr (!BF) return by_id<false, EPI_RANK>(id, g, s);
       return hipErrorInvalidValue;
+    case EPI_LSE:
+      if constexpr (!BF) return by_id<false, EPI_LSE>(id, g, s);
+      return hipErrorInvalidValue;
     default: return hipErrorInvalidValue;
   }
 }

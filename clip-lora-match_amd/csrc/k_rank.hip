@@ -56,7 +56,7 @@ __device__ __forceinline__ unsigned long long block_total(unsigned long long v, 
 // the exact route serves it); a fixed grid then walks the items, one wave per listed row. Each item
 // adds its count to out[q] (zeroed by the caller) with one integer atomicAdd, a query's first item
 // the GEMM's count as well: the sum does not depend on the order.
-constexpr int RESCORE_CHUNK = 64, RESCORE_GRID = 4096, PLAN_NT = 1024;
+constexpr int RESCORE_CHUNK = PLAN_CHUNK, RESCORE_GRID = 4096, PLAN_NT = 1024;
 
 __global__ __launch_bounds__(PLAN_NT) void rescore_plan_kernel(const int* cnt, int64_t cap, int nq, int* start) {
   __shared__ int part[PLAN_NT];
@@ -150,6 +150,13 @@ hipError_t target_scores(const float* q, const double* qn, int64_t nq, int dim, 
   const unsigned grid = (unsigned)((nq + 3) / 4);
   if (rows_f16) target_scores_kernel<u16><<<grid, 256, 0, s>>>(q, qn, nq, dim, (const u16*)rows, offset, target, t);
   else target_scores_kernel<float><<<grid, 256, 0, s>>>(q, qn, nq, dim, (const float*)rows, offset, target, t);
+  return hipGetLastError();
+}
+
+hipError_t rescore_plan(const int* cnt, int64_t cap, int64_t nq, int* plan, hipStream_t s) {
+  if (nq <= 0) return hipSuccess;
+  if (cap < 1 || !plan || nq * ((cap + RESCORE_CHUNK - 1) / RESCORE_CHUNK) > 0x7FFFFFFF) return hipErrorInvalidValue;
+  rescore_plan_kernel<<<1, PLAN_NT, 0, s>>>(cnt, cap, (int)nq, plan);
   return hipGetLastError();
 }
 

@@ -17,10 +17,19 @@ enum Epi {
   EPI_SCORE = 4,  // outf[m,n] = acc * rscale[m] * cscale[n]  (cosine scores)
   EPI_FILTER = 5,  // s = acc*rscale[m]*cscale[n]; if s >= theta[m]: append (s, base+n) to row m's
                    // candidate list (atomic slot in cnt[m], capacity cap)
-  EPI_RANK = 6     // s as above against the row's target score t = theta[m]: s > t + rank_margin is
+  EPI_RANK = 6,    // s as above against the row's target score t = theta[m]: s > t + rank_margin is
                    // counted into above[m]; otherwise s >= t - rank_margin appends base+n to row m's
                    // band list cand_i (slot from cnt[m], capacity cap). fp16, configs 1 and 8-11 only
+  EPI_LSE = 7      // s as above against the row's head floor theta[m]: s >= theta - rank_margin appends
+                   // base+n to row m's band list (cnt / cand_i / cap as EPI_RANK); every other s adds
+                   // exp2((s - theta) * lse_c) to the wave's partial lse_part[m * lse_ld + slot], slot =
+                   // (column tile) * (wave columns of the config) + wave column < lse_slots(N): every
+                   // slot a config uses is written once per live row, the others keep the caller's
+                   // zeros. fp16, configs 1 and 8-11 only
 };
+// upper bound, over the configs EPI_LSE runs on, of the slab slots per row (wave column extents are
+// 64, 96 or 128 index rows)
+inline int64_t lse_slots(int64_t N) { return N / 64 + 4; }
 constexpr bool epi_stores16(int e) { return e == EPI_STORE || e == EPI_GELU; }
 constexpr bool epi_gelu(int e) { return e == EPI_GELU; }
 
@@ -53,6 +62,8 @@ struct GemmArgs {
   const int* m_dev;
   int debug;       // diagnostics only: 1 = skip the epilogue (accumulators kept live), 2 = drop its
                    // stores, 4 = one tile per workgroup (non-persistent grid)
+  // EPI_LSE (with theta = the head floors, rank_margin, cnt / cand_i / cap / base as EPI_RANK)
+  float* lse_part; int64_t lse_ld; float lse_c;
 };
 
 hipError_t gemm(bool bf16, int epi, const GemmArgs& g, hipStream_t s);
@@ -289,6 +300,42 @@ hipError_t count_rank(const float* scores, int64_t lds, int64_t nq, int64_t C, i
                       const int64_t* g, int64_t* above, hipStream_t s);
 // out[q] = in[q] + 1
 hipError_t rank_from_above(const int64_t* above, int64_t nq, int64_t* rank, hipStream_t s);
+// rank_rescore's item plan alone: every complete band list (cnt[q] <= cap) gets max(1, ceil(cnt[q] /
+// PLAN_CHUNK)) items, plan[q] = their exclusive prefix sums, plan[nq] = the total
+constexpr int PLAN_CHUNK = 64;
+hipError_t rescore_plan(const int* cnt, int64_t cap, int64_t nq, int* plan, hipStream_t s);
+
+// ----------------------------------------------------------- log-sum-exp (k_lse.hip) ---
+// lse(q) = log sum_j exp(scale * s_j) over the exact scores s_j, in fp64.
+// The exact route: state[q] = (running maximum M, sum of exp(scale * (s - M))) folded over windows
+// of exact scores; lse_fold_init sets (-inf, 0), lse_fold adds the window scores [nq, C] (row
+// stride lds), lse_fold_finish writes lse = scale * M + log(sum) and err = 0 (err may be null).
+hipError_t lse_fold_init(double2* state, int64_t nq, hipStream_t s);
+hipError_t lse_fold(const float* scores, int64_t lds, int64_t nq, int64_t C, double scale, double2* state,
+                    hipStream_t s);
+hipError_t lse_fold_finish(const double2* state, int64_t nq, double scale, double* lse, float* err, hipStream_t s);
+// The reference route (clm_index_lse64): lse_scores64 is exact_scores without the rounding to fp32
+// (out [nq, rn] fp64, row stride ldo); lse_fold64 folds such a window of local rows [r0, r0 + C) and,
+// with target / pair given, copies the score of local row target[q] - base into pair[q] when the
+// window holds it (pair is otherwise left as it is).
+hipError_t lse_scores64(const float* q, const double* qn, int64_t nq, const void* rows, bool rows_f16, int64_t rn,
+                        int dim, double* out, int64_t ldo, hipStream_t s);
+hipError_t lse_fold64(const double* scores, int64_t lds, int64_t nq, int64_t C, double scale, double2* state,
+                      const int64_t* target, int64_t base, int64_t r0, double* pair, hipStream_t s);
+// The fast route after the EPI_LSE GEMM. lse_band_scores: the exact score of every listed band row
+// (complete lists only) into band_s [nq, cap], beside its index (rescore_plan's items; plan: nq + 1
+// ints). lse_finish, per query: head = the band rows' exp(scale * (s - M)) summed in 2^-k fixed
+// point (order-free), tail = the slab's `slots` partials summed in slot order,
+//   lse = scale * M + log(head + tail * exp(scale * (theta - M))),   err >= |lse - exact route's|
+// (DESIGN.md derives err from E = the fp16 pass's score error bound and N = the index rows);
+// redo[q] = 1 and lse / err untouched where the exact route must serve the query: band overflowed or
+// empty, non-finite theta, tail or band score, or an err that is not finite.
+hipError_t lse_band_scores(const int64_t* band, const int* cnt, int64_t cap, const float* q, const double* qn, int dim,
+                           const void* rows, bool rows_f16, int64_t offset, int64_t nq, int* plan, float* band_s,
+                           hipStream_t s);
+hipError_t lse_finish(const float* band_s, const int* cnt, int64_t cap, const float* part, int64_t slots,
+                      const float* theta, double scale, double E, int64_t N, int64_t nq, double* lse, float* err,
+                      int* redo, hipStream_t s);
 
 __host__ __device__ inline unsigned float_key(float f) {
   const unsigned b = __builtin_bit_cast(unsigned, f);

@@ -81,6 +81,25 @@ def merge_topk_gpu(scores: torch.Tensor, idx: torch.Tensor, parts: int, k: int) 
     return os_, oi
 
 
+def merge_lse(lses, errs=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(lse f64 [nq], err f64 [nq]) of the whole index from its row shards' CosineIndex.logsumexp
+    results (host function): lse = logaddexp over the shards, and the error is the share-weighted
+    combination sum_s w_s err_s, w_s = exp(lse_s - lse) the shard's share of the sum -- each
+    shard's true sum lies within e^(+-err_s) of its computed one, so the whole lies within
+    e^(+-max err), and the weighted mean is the first-order value of that. To stay a bound at any
+    size it is taken as log sum_s w_s e^(err_s) (>= the weighted mean, <= the maximum)."""
+    L = torch.stack([torch.as_tensor(v).detach().double().cpu().reshape(-1) for v in lses])
+    if errs is None:
+        E = torch.zeros_like(L)
+    else:
+        E = torch.stack([torch.as_tensor(v).detach().double().cpu().reshape(-1) for v in errs])
+    if L.shape != E.shape or L.shape[0] == 0:
+        raise ValueError("one lse vector (and one err vector) per shard expected")
+    lse = torch.logsumexp(L, dim=0)
+    err = torch.logsumexp(L + E, dim=0) - lse
+    return lse, torch.clamp(err, min=0.0)
+
+
 class ShardedIndex:
     """Row-sharded cosine index: this rank holds rows [start, stop) of n_total."""
 

@@ -12,6 +12,9 @@ resident index (clm_index_rank), so no score matrix exists on the embeddings pat
   recall_at_k / mrr / mean_average_precision            the metrics, from a rank vector
   evaluate_retrieval(image_emb, text_emb, k_values)     evaluate_model.py:186-211's result dict
   matching_accuracy(image_emb, text_emb)                evaluate_model.py:276-286
+  contrastive_loss(image_emb, text_emb, temperature)    scripts/train_lora.py:83-108 over the whole
+                                                        set (or :213-241's per-batch mean), the
+                                                        reference's model-selection signal
   CLIPEvaluator                                         evaluate_model.py:17-286, same method names
 
 Ranks order equal scores by candidate index (the search order); the reference's argsort leaves
@@ -99,6 +102,100 @@ def evaluate_retrieval(image_emb, text_emb, k_values: Sequence[int] = (1, 5, 10)
 def matching_accuracy(image_emb, text_emb) -> float:
     """share of images whose own caption scores highest (evaluate_model.py:276-286): recall@1"""
     return recall_at_k(retrieval_ranks(image_emb, text_emb), (1,))["recall@1"]
+
+
+# ------------------------------------------------------------------ contrastive loss --
+def loss_from_lse(lse_i2t, lse_t2i, pair_scores, temperature: float, err_i2t=None, err_t2i=None) -> Dict[str, float]:
+    """The symmetric InfoNCE loss of train_lora.py:83-108 from its row reductions, in fp64:
+    cross_entropy(logits, arange) = mean_i(lse_i - t_i / T) per direction, lse_i the log-sum-exp of
+    row i of scores / T and t_i = pair_scores[i] the score of pair i (the diagonal, shared by both
+    directions); loss = (loss_i2t + loss_t2i) / 2. err: the mean of the lse bounds (0 without)."""
+    li = torch.as_tensor(lse_i2t).detach().double().cpu().reshape(-1)
+    lt = torch.as_tensor(lse_t2i).detach().double().cpu().reshape(-1)
+    t = torch.as_tensor(pair_scores).detach().double().cpu().reshape(-1)
+    if li.numel() == 0 or li.numel() != lt.numel() or li.numel() != t.numel():
+        raise ValueError("one lse per direction and one pair score per pair expected, at least one pair")
+    if not (temperature > 0 and np.isfinite(temperature)):
+        raise ValueError("temperature must be finite and positive")
+    l_i = float((li - t / temperature).mean())
+    l_t = float((lt - t / temperature).mean())
+    err = 0.0
+    if err_i2t is not None and err_t2i is not None:
+        ei = torch.as_tensor(err_i2t).detach().double().cpu()
+        et = torch.as_tensor(err_t2i).detach().double().cpu()
+        err = float((ei.mean() + et.mean()) / 2)
+    return {"loss": (l_i + l_t) / 2, "loss_i2t": l_i, "loss_t2i": l_t, "err": err}
+
+
+def _cosines64(a, b) -> torch.Tensor:
+    """[len(a), len(b)] cosines in fp64 on the host"""
+    a64, b64 = torch.as_tensor(a).detach().double().cpu(), torch.as_tensor(b).detach().double().cpu()
+    return (a64 / a64.norm(dim=1, keepdim=True)) @ (b64 / b64.norm(dim=1, keepdim=True)).T
+
+
+def batched_loss(image_emb, text_emb, temperature: float, batch_size: int, scores=None) -> Dict[str, float]:
+    """train_lora.py:213-241's validation number: the mean over consecutive batches of batch_size
+    pairs (the last one may be short) of the per-batch loss, block-diagonal B x B problems done on
+    the host in fp64 from scores(image_block, text_block) -> [B, B]. Default: fp64 cosines, since
+    scores rounded to fp32 (cosine_similarity's) move this number by several 1e-9."""
+    if int(batch_size) < 1:
+        raise ValueError("batch_size must be at least 1")
+    if scores is None:
+        scores = _cosines64
+    a, b = torch.as_tensor(image_emb), torch.as_tensor(text_emb)
+    keys = ("loss", "loss_i2t", "loss_t2i")
+    total = dict.fromkeys(keys, 0.0)
+    nb = 0
+    for s0 in range(0, a.shape[0], int(batch_size)):
+        ab, bb = a[s0:s0 + batch_size], b[s0:s0 + batch_size]
+        S = torch.as_tensor(scores(ab, bb)).detach().double().cpu().reshape(ab.shape[0], bb.shape[0])
+        L = S / temperature
+        part = loss_from_lse(torch.logsumexp(L, dim=1), torch.logsumexp(L, dim=0), S.diagonal(), temperature)
+        for k in keys:
+            total[k] += part[k]
+        nb += 1
+    out = {k: total[k] / nb for k in keys}
+    out["err"] = 0.0
+    return out
+
+
+def contrastive_loss(image_emb, text_emb, temperature: float = 0.07, batch_size=None, head: int = 64,
+                     band_cap: int = 0, device=None) -> Dict[str, float]:
+    """{"loss", "loss_i2t", "loss_t2i", "err"}: the reference's CLIP contrastive loss
+    (compute_clip_contrastive_loss, train_lora.py:83-108) of N pairs against each other, without
+    the [N, N] logits: per direction CosineIndex.logsumexp streams the index once (scale = 1 / T as
+    a double) and CosineIndex.rank gives the exact pair scores. err = the mean certified bound of
+    the log-sum-exps, so |loss - the loss of the exact scores| <= err; the exact scores are fp64
+    cosines rounded to fp32, which alone moves the loss by up to 2^-24 / T (a few 1e-9 at N in the
+    hundreds). head = 0: the reference route instead (CosineIndex.logsumexp64): log-sum-exps and pair
+    scores of the unrounded fp64 cosines, the reference function on float64 tensors to fp64
+    rounding, err = 0, at the cost of an exact pass over all N x N pairs.
+    batch_size = B: the mean of the per-batch losses instead (batched_loss), the number
+    train_lora.py:213-241 prints after every epoch."""
+    a, b = torch.as_tensor(image_emb), torch.as_tensor(text_emb)
+    if a.dim() != 2 or b.dim() != 2 or a.shape != b.shape or a.shape[0] == 0:
+        raise ValueError(f"image_emb and text_emb must be [N >= 1, d] pairs, got {tuple(a.shape)} and {tuple(b.shape)}")
+    if not (temperature > 0 and np.isfinite(temperature)):
+        raise ValueError("temperature must be finite and positive")
+    if batch_size is not None:
+        return batched_loss(a, b, temperature, batch_size)
+    n = a.shape[0]
+    targets = torch.arange(n, dtype=torch.int64)
+    res = {}
+    for tag, qs, rows in (("i2t", a, b), ("t2i", b, a)):
+        idx = CosineIndex(rows.shape[1], capacity=n, device=device)
+        try:
+            idx.append(rows)
+            if int(head) <= 0 and not int(band_cap):
+                lse, t = idx.logsumexp64(qs, 1.0 / temperature, targets)
+                err = torch.zeros(n)
+            else:
+                lse, err = idx.logsumexp(qs, 1.0 / temperature, head=head, band_cap=band_cap)
+                _, t = idx.rank(qs, targets)
+            res[tag] = (lse.cpu(), err.cpu(), t.cpu())
+        finally:
+            idx.close()
+    return loss_from_lse(res["i2t"][0], res["t2i"][0], res["i2t"][2], temperature, res["i2t"][1], res["t2i"][1])
 
 
 # ------------------------------------------------------------------ similarity matrix -> ranks --
@@ -200,6 +297,13 @@ class CLIPEvaluator:
             raise ValueError("No valid samples found! Check image paths.")
         return evaluate_retrieval(img, txt, k_values)
 
+    def evaluate_loss(self, test_csv, image_root_dir, temperature: float = 0.07, batch_size=None) -> Dict[str, float]:
+        """contrastive_loss of the CSV's pairs (train_lora.py's validation loss on this adapter)"""
+        img, txt = self.encode_pairs(test_csv, image_root_dir)
+        if img.numel() == 0:
+            raise ValueError("No valid samples found! Check image paths.")
+        return contrastive_loss(img, txt, temperature, batch_size)
+
     def evaluate_matching_accuracy(self, test_csv, image_root_dir) -> float:
         img, txt = self.encode_pairs(test_csv, image_root_dir, warn=False)
         if img.numel() == 0:
@@ -208,4 +312,4 @@ class CLIPEvaluator:
 
 
 __all__ = ["retrieval_ranks", "recall_at_k", "mrr", "mean_average_precision", "evaluate_retrieval",
-           "matching_accuracy", "read_pairs", "CLIPEvaluator"]
+           "matching_accuracy", "contrastive_loss", "loss_from_lse", "batched_loss", "read_pairs", "CLIPEvaluator"]

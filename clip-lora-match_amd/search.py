@@ -165,6 +165,68 @@ class CosineIndex:
         C.check(C.lib().clm_index_stats2(self._h, v, 11))
         return {"band": v[7], "exact": v[8], "overflow": v[9], "band_rows": v[10]}
 
+    # ------------------------------------------------------------ log-sum-exp --
+    def logsumexp(self, queries, scale: float, head: int = 64, band_cap: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(lse [nq] f64, err [nq] f32) on the GPU: lse = log sum_j exp(scale * score_j) over every row
+        of the index, score_j the exact score of `search`, in fp64 and without a [nq, N] matrix
+        (clm_index_lse). head > 0: the fast route -- search(q, min(head, N)) gives each query's head
+        floor (its last exact score), one fp16 MFMA pass sums the rows below it on chip and lists the
+        rest for an exact re-score; err >= |lse - the exact route's lse|, certified. head = 0 (or a
+        small problem, or band_cap | CLM_LSE_EXACT): the exact route, err = 0. Two calls return the
+        same bits on either route. ValueError for an empty index or a scale that is not finite and
+        positive."""
+        q = self._queries(queries)
+        nq = q.shape[0]
+        n = len(self)
+        lse = torch.empty((nq,), dtype=torch.float64, device=self.device)
+        err = torch.empty((nq,), dtype=torch.float32, device=self.device)
+        floor = None
+        if int(head) > 0 and n > 0 and nq > 0 and not (int(band_cap) > 0 and int(band_cap) & C.CLM_LSE_EXACT):
+            floor = self.search(q, min(int(head), n))[0][:, -1].contiguous()
+        code = C.CLM_F32 if q.dtype == torch.float32 else C.CLM_F16
+        C.check(C.lib().clm_index_lse(self._h, C.ptr(q), code, nq, float(scale),
+                                      C.ptr(floor) if floor is not None else None, C.ptr(lse), C.ptr(err),
+                                      int(band_cap), C.stream_of(self.device)), "clm_index_lse")
+        return lse, err
+
+    def logsumexp64(self, queries, scale: float, targets=None) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+        """(lse [nq] f64, pair [nq] f64 or None): the reference route (clm_index_lse64). As the exact
+        route of `logsumexp`, but on the unrounded fp64 cosines instead of the exact scores (fp64
+        cosines rounded to fp32), and pair[i] = the fp64 cosine of query i and row targets[i] (global
+        row ids, as in `rank`): what the same reduction gives on float64 tensors, to fp64 rounding."""
+        q = self._queries(queries)
+        nq = q.shape[0]
+        lse = torch.empty((nq,), dtype=torch.float64, device=self.device)
+        tg = pair = None
+        if targets is not None:
+            tg = torch.as_tensor(targets).to(device=self.device, dtype=torch.int64).contiguous()
+            if tg.shape != (nq,):
+                raise ValueError(f"targets must be [{nq}], got {tuple(tg.shape)}")
+            pair = torch.empty((nq,), dtype=torch.float64, device=self.device)
+        code = C.CLM_F32 if q.dtype == torch.float32 else C.CLM_F16
+        C.check(C.lib().clm_index_lse64(self._h, C.ptr(q), code, nq, float(scale),
+                                        C.ptr(tg) if tg is not None else None, C.ptr(lse),
+                                        C.ptr(pair) if pair is not None else None, C.stream_of(self.device)),
+                "clm_index_lse64")
+        return lse, pair
+
+    def softmax_topk(self, queries, k: int, scale: float = 100.0, head: int = 64):
+        """(probs [nq, k] f64, idx [nq, k] i64, err [nq] f32): the k most probable rows of
+        softmax(scale * score) over the whole index, probs = exp(scale * score - lse) from `search`
+        and `logsumexp`; err bounds lse (so a probability is off by a factor within e^(+-err)).
+        Slots past the index size hold (0, -1)."""
+        s, i = self.search(queries, int(k))
+        lse, err = self.logsumexp(queries, scale, head=head)
+        p = torch.exp(float(scale) * s.double() - lse[:, None])
+        return torch.where(i >= 0, p, torch.zeros_like(p)), i, err
+
+    def lse_stats(self) -> dict:
+        """logsumexp queries served by the MFMA pass (`fast`), by the exact route (`exact`), and those
+        whose band list overflowed its capacity (`overflow`; they are among `exact`)"""
+        v = (ctypes.c_int64 * 14)()
+        C.check(C.lib().clm_index_stats2(self._h, v, 14))
+        return {"fast": v[11], "exact": v[12], "overflow": v[13]}
+
     # ------------------------------------------------------------ shard file --
     def save_shard(self, path: Union[str, Path], meta: Optional[dict] = None, chunk_rows: int = 1 << 20) -> None:
         """Write the index's internal state (fp16 operands, fp32 inverse norms, the fp32 rows if

@@ -23,6 +23,12 @@
  *   clm_index_rank,            (new) the rank of each query's ground-truth row in the whole index,
  *   clm_index_count_above      what scripts/evaluate_model.py:60-103 (compute_recall_at_k / _mrr /
  *                              _map) reads off argsort positions of a full [nq, N] matrix
+ *   clm_index_lse              (new) log sum_j exp(scale * score_j) per query over the whole index:
+ *                              the row reduction of compute_clip_contrastive_loss
+ *                              (scripts/train_lora.py:83-108, evaluated :213-241) and the
+ *                              normaliser of softmax match probabilities, without a [nq, N] matrix
+ *   clm_index_lse64            (new) the same reduction and the pair scores on unrounded fp64
+ *                              cosines: that function on float64 tensors
  *   clm_cosine_scores          cosine_similarity similarity.py:10-33
  *   clm_topk_merge             (new) merge of per-shard top-k lists for the
  *                              8-GPU sharded search
@@ -224,18 +230,61 @@ int clm_index_count_above(clm_index* idx, const void* q, int q_dtype, int64_t nq
 int clm_index_rank(clm_index* idx, const void* q, int q_dtype, int64_t nq, const int64_t* target,
                    int64_t* out_rank, float* out_score, int band_cap, void* stream);
 
+/* Streaming log-sum-exp. With s_j the exact score of row j (as above),
+ *
+ *     lse(q) = log sum_j exp(scale * s_j)
+ *
+ * evaluated in fp64, max-shifted, rows in index order; a NaN score makes the result NaN
+ * (torch.logsumexp's behaviour). The exact route computes just that from windows of exact scores
+ * folded into a running (maximum, sum) per query: bit-reproducible, err = 0.
+ * The fast route takes a head floor per query, head_floor[i] (typically the k-th exact score of
+ * clm_index_search): one fp16 MFMA pass lists the rows whose fp16-pass score is within a margin of
+ * the floor or above it (re-scored exactly, summed in fp64) and sums exp(scale * (score - floor)) of
+ * all the others on chip in fp32; out_err[i] >= |out_lse[i] - the exact route's result|, a certified
+ * bound from the fp16 pass's score error and the fp32 arithmetic. No floating-point
+ * atomics: two calls return the same bits. No buffer grows with nq x size.
+ * The whole call takes the exact route when head_floor is NULL, the index holds a zero or non-finite
+ * row norm, dim > 8192, size > 2^31 - 1, nq x size <= 2^24 (unless CLM_LSE_FAST), CLM_LSE_EXACT or
+ * $CLM_SEARCH_FULL=1; a single query does when its band list overflowed the capacity or is empty
+ * (a floor above every score) or its floor is not finite. band_cap: as in clm_index_rank (capacity
+ * in the CLM_RANK_CAP_MASK bits, 0 = default). q [nq, dim] CLM_F32|CLM_F16; out_lse [nq] doubles,
+ * out_err [nq] floats or NULL; every pointer host or device. scale is a double on purpose: 1 / 0.07
+ * rounded to fp32 moves a loss by about 1e-7.
+ * A row-sharded index is additive: lse of the whole = logaddexp over the shards' results, each shard
+ * called with floors of its own, and the largest shard bound bounds the merged error.
+ * CLM_E_ARG: an empty index, a null q or out_lse, a dtype other than f32 / f16, nq < 0, a scale that
+ * is not finite and positive. */
+enum { CLM_LSE_EXACT = 1 << 30, CLM_LSE_FAST = 1 << 29 };
+int clm_index_lse(clm_index* idx, const void* q, int q_dtype, int64_t nq, double scale, const float* head_floor,
+                  double* out_lse, float* out_err, int band_cap, void* stream);
+
+/* The reference route. An exact score is an fp64 cosine rounded once to fp32, so clm_index_lse's
+ * result is within scale * 2^-25 of the log-sum-exp of the unrounded cosines, and a loss built on it
+ * and on clm_index_rank's scores sits a few 1e-9 from the same loss in float64. This call is
+ * clm_index_lse's exact route (the same row windows, the same fold) with no rounding to fp32 at all:
+ * out_lse[i] = log sum_j exp(scale * c_ij), c_ij = dot / (|q_i| |row_j|) in fp64, and, when out_pair
+ * is given, out_pair[i] = c_ij of row target[i] (a global row id as in clm_index_rank; NaN when the
+ * index does not hold it). Bit-reproducible; a NaN cosine makes the result NaN. The cost is that of
+ * the exact route: for model selection by the reference's own number, not for serving.
+ * q [nq, dim] CLM_F32|CLM_F16; target [nq] or NULL; out_lse [nq], out_pair [nq] or NULL; every pointer
+ * host or device. CLM_E_ARG: as clm_index_lse, and out_pair without target. */
+int clm_index_lse64(clm_index* idx, const void* q, int q_dtype, int64_t nq, double scale, const int64_t* target,
+                    double* out_lse, double* out_pair, void* stream);
+
 /* search-path counters since creation: queries served by the sampled single-pass bounded
  * search (`filtered`), by the exact scan or the fp16-scan-bounded search (`exact`), and
  * bounded queries whose candidate list overflowed (redone by a whole-list pass, or by the exact
  * scan when the list is longer than 8192 / k chunks of 4096) */
 int clm_index_stats(const clm_index* idx, int64_t* filtered, int64_t* exact, int64_t* overflow);
-/* out[0..n), n <= 11: sampled bounded, fp16-scan bounded, full exact scan, overflow re-runs, then the
+/* out[0..n), n <= 14: sampled bounded, fp16-scan bounded, full exact scan, overflow re-runs, then the
  * sampled queries whose filter pass ran on the G2 256 x 192 tiles / on gemm_kernel 256 x 256 (chosen
  * per query block from the block's sampled candidate counts: near-duplicate blocks take the latter),
  * then the queries served by the small-batch streaming search (nq <= 16 on a large index: one pass
  * over the fp16 rows, thresholds from 256-row chunk maxima), then the rank / count_above queries
  * served by the band pass, by the exact route, those of the latter whose band list overflowed, and
- * the band rows re-scored for the band-served queries */
+ * the band rows re-scored for the band-served queries, then the clm_index_lse queries served by the
+ * fast route, by the exact route (clm_index_lse64's among them), and those whose band list overflowed
+ * its capacity */
 int clm_index_stats2(const clm_index* idx, int64_t* out, int n);
 
 /* full cosine matrix, exact: out [nq, n] f32 = fp32(cos64(q_i, c_j)), any dim */
