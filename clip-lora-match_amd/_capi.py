@@ -81,6 +81,8 @@ def lib():
         "clm_index_size": (c_int64, [c_void_p]),
         "clm_index_reset": (c_int, [c_void_p]),
         "clm_index_set_offset": (c_int, [c_void_p, c_int64]),
+        "clm_index_remove": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
+        "clm_index_update": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p]),
         "clm_index_read": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
         "clm_index_search": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
         "clm_index_count_above": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_int,
@@ -146,7 +148,7 @@ EXPORTED = (
     "clm_model_desc_size", "clm_prof_enable", "clm_prof_read", "clm_gemm", "clm_gemm_num_configs",
     "clm_attention", "clm_attention_ex", "clm_gemm_scores16", "clm_layernorm", "clm_debug_set",
     "clm_scan16", "clm_scan16_waves", "clm_collect_ge", "clm_index_count_above", "clm_index_rank",
-    "clm_index_lse", "clm_index_lse64",
+    "clm_index_lse", "clm_index_lse64", "clm_index_remove", "clm_index_update",
 )
 CLM_EPI_STORE, CLM_EPI_GELU, CLM_EPI_RESID, CLM_EPI_SCORE = 0, 1, 2, 4
 CLM_PROF_GEMM, CLM_PROF_ATTN, CLM_PROF_LN, CLM_PROF_OTHER = 0, 1, 2, 3

@@ -232,6 +232,8 @@ struct clm_index {
   u16* samp = nullptr; float* samp_inv = nullptr; int64_t samp_S = 0, samp_n = -1, samp_cap = 0;
   // order keys {min, max} of inv[0, n) for the filter GEMM's skip test, rebuilt with the sample
   unsigned* inv_keys = nullptr; int64_t inv_keys_n = -1;
+  // staging of clm_index_remove / clm_index_update: MUTATE_STAGE_BYTES, allocated by the first of them
+  void* mut = nullptr;
   // queries served by: [0] sampled bounded search, [1] the full exact scan, [2] overflow re-runs,
   // [3] bounded search with the chunked fp16 scan as step 1
   // [4] / [5]: queries whose filter pass ran on G2 256 x 192 / gemm_kernel 256 x 256 (dense blocks)
@@ -1330,7 +1332,7 @@ int clm_index_destroy(clm_index* x) {
   DeviceGuard g(x->dev);
   (void)hipDeviceSynchronize();
   for (void* p : {(void*)x->rows, (void*)x->inv, (void*)x->rows32, x->ws, x->ws2, x->ws3, x->ws4, (void*)x->samp,
-                  (void*)x->samp_inv, (void*)x->inv_keys})
+                  (void*)x->samp_inv, (void*)x->inv_keys, x->mut})
     if (p) (void)hipFree(p);
   delete x;
   return CLM_OK;
@@ -1493,6 +1495,172 @@ int clm_index_reset(clm_index* x) {
 int clm_index_set_offset(clm_index* x, int64_t off) {
   if (!x || off < 0 || off > MAX_GLOBAL_OFFSET) return fail(CLM_E_ARG, "index offset: 0 <= offset <= 2^62");
   x->offset = off;
+  return CLM_OK;
+}
+
+// ---- in-place mutation (clm_index_remove / clm_index_update, k_mutate.hip) -------------------
+// One staging buffer of a fixed size, whatever the index holds: removal moves the rows above the
+// first removed one chunk by chunk through it, update converts the new rows into it batch by batch.
+constexpr size_t MUTATE_STAGE_BYTES = (size_t)64 << 20;
+
+static int mutate_stage(clm_index* x) {
+  if (x->mut) return CLM_OK;
+  if (hipMalloc(&x->mut, MUTATE_STAGE_BYTES) != hipSuccess) {
+    (void)hipGetLastError();
+    x->mut = nullptr;
+    return fail(CLM_E_OOM, "index mutation: staging allocation failed");
+  }
+  return CLM_OK;
+}
+
+// rows per pass: what the staging buffer holds at row_bytes each, lowered by $CLM_MUTATE_CHUNK_ROWS
+// (tests: chunk boundaries at a few thousand rows)
+static int64_t mutate_chunk_rows(size_t row_bytes) {
+  int64_t r = std::max<int64_t>(1, (int64_t)(MUTATE_STAGE_BYTES / row_bytes));
+  const char* e = getenv("CLM_MUTATE_CHUNK_ROWS");
+  if (e && atoll(e) >= 1) r = std::min<int64_t>(r, atoll(e));
+  return r;
+}
+
+// the caller's global ids (host or device) as local rows on the host; CLM_E_ARG for one outside the index
+static int mutate_local_ids(const clm_index* x, const int64_t* ids, int64_t n, std::vector<int64_t>& loc,
+                            const char* what) {
+  loc.resize((size_t)n);
+  if (is_device_ptr(ids)) HIPCHK(hipMemcpy(loc.data(), ids, (size_t)n * 8, hipMemcpyDeviceToHost));
+  else std::memcpy(loc.data(), ids, (size_t)n * 8);
+  for (int64_t& v : loc) {
+    if (v < x->offset || v - x->offset >= x->n)
+      return fail(CLM_E_ARG, std::string(what) + ": id " + std::to_string(v) + " is outside [offset, offset + size)");
+    v -= x->offset;
+  }
+  return CLM_OK;
+}
+
+int clm_index_remove(clm_index* x, const int64_t* ids, int64_t n_ids, void* stream) {
+  if (!x || n_ids < 0 || (n_ids > 0 && !ids)) return fail(CLM_E_ARG, "index remove: bad argument");
+  if (n_ids == 0) return CLM_OK;
+  DeviceGuard g(x->dev);
+  hipStream_t st = (hipStream_t)stream;
+  std::vector<int64_t> rem;
+  int r = mutate_local_ids(x, ids, n_ids, rem, "index remove");
+  if (r) return r;
+  std::sort(rem.begin(), rem.end());
+  rem.erase(std::unique(rem.begin(), rem.end()), rem.end());
+  const int64_t m = (int64_t)rem.size(), n = x->n, dim = x->dim;
+  HIPCHK(hipStreamSynchronize(st));
+  if ((r = mutate_stage(x))) return r;
+  x->samp_n = -1;
+  x->inv_keys_n = -1;
+  int64_t* drem = nullptr;   // the sorted list on the device, for the gather's binary search
+  if (hipMalloc(&drem, (size_t)m * 8) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(CLM_E_OOM, "index remove: id list allocation failed");
+  }
+  hipError_t e = hipMemcpyAsync(drem, rem.data(), (size_t)m * 8, hipMemcpyHostToDevice, st);
+  // Stable compaction of rows [rem[0], n) in stream order, R source rows at a time. A chunk's
+  // survivors land at [d0, d0 + surv), d0 = s0 - (removed rows below s0): at or below their sources,
+  // above every row an earlier chunk wrote and below every row a later chunk reads. Only the chunk's
+  // own sources can overlap that range, so it is gathered into the staging buffer and copied down --
+  // or straight to the destination once the range ends at or below s0.
+  const bool has32 = x->rows32 != nullptr;
+  const int64_t R = mutate_chunk_rows((size_t)dim * (has32 ? 6 : 2) + 4);
+  u16* s16 = (u16*)x->mut;
+  float* s32 = has32 ? (float*)((char*)x->mut + (size_t)R * dim * 2) : nullptr;
+  float* sinv = (float*)((char*)x->mut + (size_t)R * dim * (has32 ? 6 : 2));
+  int64_t c = 0;   // removed rows below s0
+  for (int64_t s0 = rem[0]; s0 < n && e == hipSuccess; s0 += R) {
+    const int64_t s1 = std::min(n, s0 + R);
+    const int64_t c1 = std::lower_bound(rem.begin() + c, rem.end(), s1) - rem.begin();
+    const int64_t surv = (s1 - s0) - (c1 - c), d0 = s0 - c;
+    if (surv > 0) {
+      u16* d16 = x->rows + (size_t)d0 * dim;
+      float* d32 = has32 ? x->rows32 + (size_t)d0 * dim : nullptr;
+      float* dinv = x->inv + d0;
+      const bool direct = d0 + surv <= s0;
+      e = gather_rows(x->rows, x->rows32, x->inv, s0, s1 - s0, (int)dim, drem + c, c1 - c, direct ? d16 : s16,
+                      direct ? d32 : s32, direct ? dinv : sinv, st);
+      if (!direct) {
+        if (e == hipSuccess) e = hipMemcpyAsync(d16, s16, (size_t)surv * dim * 2, hipMemcpyDeviceToDevice, st);
+        if (e == hipSuccess && has32)
+          e = hipMemcpyAsync(d32, s32, (size_t)surv * dim * 4, hipMemcpyDeviceToDevice, st);
+        if (e == hipSuccess) e = hipMemcpyAsync(dinv, sinv, (size_t)surv * 4, hipMemcpyDeviceToDevice, st);
+      }
+    }
+    c = c1;
+  }
+  const hipError_t es = hipStreamSynchronize(st);
+  (void)hipFree(drem);
+  if (e == hipSuccess) e = es;
+  if (e != hipSuccess) return fail(CLM_E_HIP, std::string("index remove: ") + hipGetErrorString(e));
+  x->n = n - m;
+  return CLM_OK;
+}
+
+int clm_index_update(clm_index* x, const int64_t* ids, const void* rows, int dtype, int64_t n, void* stream) {
+  if (!x || n < 0 || (n > 0 && (!ids || !rows))) return fail(CLM_E_ARG, "index update: bad argument");
+  if (dtype != CLM_F32 && dtype != CLM_F16) return fail(CLM_E_ARG, "index update: rows must be f32 or f16");
+  if (n == 0) return CLM_OK;
+  DeviceGuard g(x->dev);
+  hipStream_t st = (hipStream_t)stream;
+  std::vector<int64_t> loc;
+  int r = mutate_local_ids(x, ids, n, loc, "index update");
+  if (r) return r;
+  {
+    std::vector<int64_t> s(loc);
+    std::sort(s.begin(), s.end());
+    if (std::adjacent_find(s.begin(), s.end()) != s.end()) return fail(CLM_E_ARG, "index update: duplicate id");
+  }
+  const int64_t dim = x->dim;
+  HIPCHK(hipStreamSynchronize(st));
+  if ((r = mutate_stage(x))) return r;
+  if (dtype == CLM_F32 && !x->rows32) {   // as clm_index_append: the first fp32 rows start the fp32 copy
+    if (hipMalloc(&x->rows32, (size_t)x->cap * dim * sizeof(float)) != hipSuccess) {
+      (void)hipGetLastError();
+      x->rows32 = nullptr;
+      return fail(CLM_E_OOM, "fp32 row copy allocation failed");
+    }
+    KCHK(f16_to_f32_rows(x->rows, x->n, (int)dim, x->rows32, st));
+  }
+  x->samp_n = -1;   // n stays: nothing else would rebuild the sample and the order keys
+  x->inv_keys_n = -1;
+  // per batch of B rows, in the staging buffer: the rows as given (when they come from the host or
+  // are not 16-byte aligned), their fp16 operands, their fp32 form (f16 rows into an index with the
+  // fp32 copy), the local ids, the inverse norms -- converted by append's own routines, then scattered
+  const bool has32 = x->rows32 != nullptr;
+  const size_t esz = dtype_size(dtype);
+  const int64_t B = mutate_chunk_rows((size_t)dim * 10 + 12);
+  char* base = (char*)x->mut;
+  void* ssrc = base;
+  u16* s16 = (u16*)(base + (size_t)B * dim * 4);
+  float* s32 = (float*)(base + (size_t)B * dim * 6);
+  int64_t* sid = (int64_t*)(base + (size_t)B * dim * 10);
+  float* sinv = (float*)(base + (size_t)B * dim * 10 + (size_t)B * 8);
+  const bool dev_rows = is_device_ptr(rows);
+  hipError_t e = hipSuccess;
+  for (int64_t b0 = 0; b0 < n && e == hipSuccess; b0 += B) {
+    const int64_t nb = std::min(B, n - b0);
+    const void* src = (const char*)rows + (size_t)b0 * dim * esz;
+    if (!dev_rows || ((uintptr_t)src & 15)) {
+      e = hipMemcpyAsync(ssrc, src, (size_t)nb * dim * esz, dev_rows ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
+                         st);
+      src = ssrc;
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(sid, loc.data() + b0, (size_t)nb * 8, hipMemcpyHostToDevice, st);
+    const float* src32 = nullptr;
+    if (e == hipSuccess && has32) {
+      if (dtype == CLM_F32) src32 = (const float*)src;
+      else {
+        e = f16_to_f32_rows((const u16*)src, nb, (int)dim, s32, st);
+        src32 = s32;
+      }
+    }
+    if (e == hipSuccess)
+      e = rows_to_f16(src, dtype == CLM_F32 ? 0 : 1, nb, (int)dim, s16, sinv, st, dtype == CLM_F32 ? 2 : 0);
+    if (e == hipSuccess) e = scatter_rows(s16, src32, sinv, sid, 0, nb, (int)dim, x->rows, x->rows32, x->inv, st);
+  }
+  const hipError_t es = hipStreamSynchronize(st);
+  if (e == hipSuccess) e = es;
+  if (e != hipSuccess) return fail(CLM_E_HIP, std::string("index update: ") + hipGetErrorString(e));
   return CLM_OK;
 }
 

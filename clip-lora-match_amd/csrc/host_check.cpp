@@ -8,7 +8,8 @@
 //  * with a HIP device: the resident-index lifecycle (create, f16 + f32 appends that grow the
 //    capacity, search on the scan and bounded paths, ranks on every route and their argument
 //    validation, the log-sum-exp on every route and its argument validation, read-back, offset,
-//    reset, destroy),
+//    reset, destroy), remove / update round trips against a freshly built index and their
+//    argument validation,
 //    clm_cosine_scores / clm_topk_merge / clm_l2_normalize / clm_fuse_queries on host buffers,
 //    each checked against a scalar host reference.
 // Exit code 0 = all checks passed (the sanitizers abort the process on their own findings).
@@ -87,6 +88,104 @@ static void argument_checks() {
   CHECK(clm_index_lse(nullptr, rq, CLM_F32, 1, 100.0, rs, rl, rs, 0, nullptr) == CLM_E_ARG);
   CHECK(clm_index_lse(nullptr, rq, CLM_F32, 0, 100.0, nullptr, nullptr, nullptr, 0, nullptr) == CLM_E_ARG);
   CHECK(clm_index_lse64(nullptr, rq, CLM_F32, 1, 100.0, nullptr, rl, nullptr, nullptr) == CLM_E_ARG);
+  // remove / update: null index, whatever else is passed
+  CHECK(clm_index_remove(nullptr, rt, 1, nullptr) == CLM_E_ARG);
+  CHECK(clm_index_remove(nullptr, nullptr, 0, nullptr) == CLM_E_ARG);
+  CHECK(clm_index_update(nullptr, rt, rq, CLM_F32, 1, nullptr) == CLM_E_ARG);
+  CHECK(clm_index_update(nullptr, nullptr, nullptr, CLM_F32, 0, nullptr) == CLM_E_ARG);
+}
+
+// the index's whole internal state, as clm_index_export gives it
+struct IndexState {
+  int64_t n = -1;
+  int has32 = -1;
+  std::vector<uint16_t> r16;
+  std::vector<float> inv, r32;
+  bool operator==(const IndexState& o) const {
+    return n == o.n && has32 == o.has32 && r16 == o.r16 && r32 == o.r32 &&
+           (inv.empty() || std::memcmp(inv.data(), o.inv.data(), inv.size() * 4) == 0);
+  }
+};
+static IndexState state_of(clm_index* idx, int dim) {
+  IndexState s;
+  s.n = clm_index_size(idx);
+  s.has32 = clm_index_has_f32(idx);
+  s.r16.resize((size_t)s.n * dim);
+  s.inv.resize((size_t)s.n);
+  if (s.has32 == 1) s.r32.resize((size_t)s.n * dim);
+  CHECK(clm_index_export(idx, 0, s.n, s.r16.data(), s.inv.data(), s.has32 == 1 ? s.r32.data() : nullptr, nullptr) ==
+        CLM_OK);
+  return s;
+}
+
+// remove / update round trips against a fresh index (one built by appending the final rows in
+// order, each run in its final dtype), and their argument validation on a live index
+static void mutate_checks() {
+  const int dim = 128, n16 = 300, n32 = 700, n = n16 + n32;
+  std::vector<float> rows((size_t)n * dim);
+  for (auto& v : rows) v = frand();
+  std::vector<uint16_t> h16((size_t)n16 * dim);
+  for (size_t i = 0; i < h16.size(); ++i) {
+    const _Float16 h = (_Float16)rows[i];
+    std::memcpy(&h16[i], &h, 2);
+  }
+  clm_index* idx = nullptr;
+  CHECK(clm_index_create(0, 8, dim, &idx) == CLM_OK);
+  if (!idx) return;
+  CHECK(clm_index_append(idx, h16.data(), CLM_F16, n16, nullptr) == CLM_OK);
+  CHECK(clm_index_append(idx, rows.data() + (size_t)n16 * dim, CLM_F32, n32, nullptr) == CLM_OK);
+  CHECK(clm_index_set_offset(idx, 1000) == CLM_OK);
+  const IndexState before = state_of(idx, dim);
+  // argument validation: nothing changes
+  int64_t ids[4] = {1000, 1000 + n - 1, 1005, 1005};
+  CHECK(clm_index_remove(idx, nullptr, 2, nullptr) == CLM_E_ARG);
+  CHECK(clm_index_remove(idx, ids, -1, nullptr) == CLM_E_ARG);
+  CHECK(clm_index_update(idx, nullptr, rows.data(), CLM_F32, 2, nullptr) == CLM_E_ARG);
+  CHECK(clm_index_update(idx, ids, nullptr, CLM_F32, 2, nullptr) == CLM_E_ARG);
+  CHECK(clm_index_update(idx, ids, rows.data(), CLM_F32, -1, nullptr) == CLM_E_ARG);
+  CHECK(clm_index_update(idx, ids, rows.data(), CLM_BF16, 2, nullptr) == CLM_E_ARG);
+  CHECK(clm_index_update(idx, ids, rows.data(), CLM_F32, 4, nullptr) == CLM_E_ARG);   // 1005 twice
+  for (int64_t bad : {(int64_t)-1, (int64_t)999, (int64_t)1000 + n, (int64_t)1 << 40}) {
+    int64_t b[2] = {1001, bad};
+    CHECK(clm_index_remove(idx, b, 2, nullptr) == CLM_E_ARG);
+    CHECK(clm_index_update(idx, b, rows.data(), CLM_F32, 2, nullptr) == CLM_E_ARG);
+  }
+  CHECK(clm_index_remove(idx, ids, 0, nullptr) == CLM_OK);
+  CHECK(clm_index_update(idx, ids, rows.data(), CLM_F32, 0, nullptr) == CLM_OK);
+  CHECK(state_of(idx, dim) == before);
+  // remove: every 7th row, the first, the last, 1005 twice, unsorted; chunks of 64 rows
+  setenv("CLM_MUTATE_CHUNK_ROWS", "64", 1);
+  std::vector<int64_t> rem = {1000 + n - 1, 1005, 1000, 1005};
+  for (int j = 7; j < n - 1; j += 7) rem.push_back(1000 + j);
+  CHECK(clm_index_remove(idx, rem.data(), (int64_t)rem.size(), nullptr) == CLM_OK);
+  std::vector<char> gone(n, 0);
+  for (int64_t v : rem) gone[v - 1000] = 1;
+  // update: three survivors, f32 rows (one in the fp16 run, so the fresh index appends it as f32)
+  const int64_t upd[3] = {1000 + 400, 1000 + 2, 1000 + 150};
+  std::vector<float> fresh_rows((size_t)3 * dim);
+  for (auto& v : fresh_rows) v = 3.0f * frand();
+  CHECK(clm_index_update(idx, upd, fresh_rows.data(), CLM_F32, 3, nullptr) == CLM_OK);
+  unsetenv("CLM_MUTATE_CHUNK_ROWS");
+  // the fresh index: the final rows in order, run by run
+  clm_index* fr = nullptr;
+  CHECK(clm_index_create(0, 8, dim, &fr) == CLM_OK);
+  if (fr) {
+    int64_t pos = 0;
+    for (int j = 0; j < n; ++j) {
+      if (gone[j]) continue;
+      int u = -1;
+      for (int t = 0; t < 3; ++t)
+        if (upd[t] - 1000 == pos) u = t;
+      if (u >= 0) CHECK(clm_index_append(fr, &fresh_rows[(size_t)u * dim], CLM_F32, 1, nullptr) == CLM_OK);
+      else if (j < n16) CHECK(clm_index_append(fr, &h16[(size_t)j * dim], CLM_F16, 1, nullptr) == CLM_OK);
+      else CHECK(clm_index_append(fr, &rows[(size_t)j * dim], CLM_F32, 1, nullptr) == CLM_OK);
+      ++pos;
+    }
+    CHECK(clm_index_size(idx) == pos);
+    CHECK(state_of(idx, dim) == state_of(fr, dim));
+    CHECK(clm_index_destroy(fr) == CLM_OK);
+  }
+  CHECK(clm_index_destroy(idx) == CLM_OK);
 }
 
 static double cos64(const float* a, const float* b, int dim) {
@@ -349,6 +448,7 @@ int main() {
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0) {
     device_checks();
+    mutate_checks();
     std::printf("host_check: argument + device checks, %d failure(s)\n", failures);
   } else {
     (void)hipGetLastError();

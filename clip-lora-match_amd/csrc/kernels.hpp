@@ -337,6 +337,17 @@ hipError_t lse_finish(const float* band_s, const int* cnt, int64_t cap, const fl
                       const float* theta, double scale, double E, int64_t N, int64_t nq, double* lse, float* err,
                       int* redo, hipStream_t s);
 
+// ----------------------------------------------------------- index mutation (k_mutate.hip) ---
+// Whole-row movers over the index's three arrays (fp16 rows, fp32 rows or null, fp32 inverse
+// norms), 16-byte loads and stores. gather_rows: the rows of [s0, s0 + rows) that are not in rem
+// (sorted, distinct, all inside that range; m of them) packed in order into out16 / out32 / out_inv
+// (slot 0 = the first survivor). scatter_rows: staged row i -> row ids[i] - offset (ids distinct
+// and inside the index: the caller's check).
+hipError_t gather_rows(const u16* rows16, const float* rows32, const float* inv, int64_t s0, int64_t rows, int dim,
+                       const int64_t* rem, int64_t m, u16* out16, float* out32, float* out_inv, hipStream_t s);
+hipError_t scatter_rows(const u16* src16, const float* src32, const float* src_inv, const int64_t* ids, int64_t offset,
+                        int64_t n, int dim, u16* rows16, float* rows32, float* inv, hipStream_t s);
+
 __host__ __device__ inline unsigned float_key(float f) {
   const unsigned b = __builtin_bit_cast(unsigned, f);
   return (b & 0x80000000u) ? ~b : (b | 0x80000000u);

@@ -100,6 +100,32 @@ def merge_lse(lses, errs=None) -> Tuple[torch.Tensor, torch.Tensor]:
     return lse, torch.clamp(err, min=0.0)
 
 
+def ranges_after_remove(sizes, starts, ids):
+    """Bookkeeping of ShardedIndex.remove (host function). Shard r holds global rows
+    [starts[r], starts[r] + sizes[r]), the shards in global order. For the global ids to remove
+    (any order, duplicates count once) returns (local, new_sizes, new_starts): local[r] = the
+    sorted distinct ids that fall in shard r (still global ids, as clm_index_remove takes them),
+    new_sizes[r] = what shard r keeps, new_starts = the exclusive prefix sums of new_sizes -- the
+    survivors renumbered contiguously in order. ValueError for an id no shard holds."""
+    sizes, starts = [int(s) for s in sizes], [int(s) for s in starts]
+    if len(sizes) != len(starts):
+        raise ValueError("one size and one start per shard expected")
+    local = [[] for _ in sizes]
+    for g in sorted({int(i) for i in ids}):
+        for r, (s, n) in enumerate(zip(starts, sizes)):
+            if s <= g < s + n:
+                local[r].append(g)
+                break
+        else:
+            raise ValueError(f"global id {g} is in no shard")
+    new_sizes = [n - len(loc) for n, loc in zip(sizes, local)]
+    new_starts, acc = [], 0
+    for n in new_sizes:
+        new_starts.append(acc)
+        acc += n
+    return local, new_sizes, new_starts
+
+
 class ShardedIndex:
     """Row-sharded cosine index: this rank holds rows [start, stop) of n_total."""
 
@@ -116,11 +142,46 @@ class ShardedIndex:
             local_factory = lambda: CosineIndex(dim, capacity=max(self.stop - self.start, 1), device=device)  # noqa
         self.local = local_factory()
         self.local.set_offset(self.start)
+        # every rank's shard size (shard_range until a remove changes them)
+        self._sizes = [e - s for s, e in (shard_range(n_total, r, self.world) for r in range(self.world))]
 
     def append_shard(self, rows: torch.Tensor) -> None:
         if rows.shape[0] != self.stop - self.start:
             raise ValueError("rows must be exactly this rank's shard")
         self.local.append(rows)
+
+    def remove(self, global_ids) -> int:
+        """Remove rows by global id; every rank passes the same ids (a collective call). Each rank
+        removes the ids inside its [start, stop) from its resident shard in place, one all_gather
+        of the new local sizes follows, and every rank renumbers: start / stop / the local offset
+        become the exclusive prefix sums of those sizes, so the survivors are numbered
+        contiguously in their old order -- as in one index that removed the same ids. Returns the
+        number of rows removed over all shards. ValueError (on every rank, before anything
+        changes) for an id outside [0, n_total)."""
+        starts, acc = [], 0
+        for n in self._sizes:
+            starts.append(acc)
+            acc += n
+        local, new_sizes, new_starts = ranges_after_remove(self._sizes, starts, global_ids)
+        if local[self.rank]:
+            self.local.remove(local[self.rank])
+        mine = torch.tensor([len(self.local)], dtype=torch.int64, device=getattr(self.local, "device", "cpu"))
+        if self.world > 1:
+            got = torch.empty((self.world,), dtype=torch.int64, device=mine.device)
+            dist.all_gather_into_tensor(got, mine, group=self.group)
+        else:
+            got = mine
+        sizes = [int(v) for v in got.tolist()]
+        if sizes != new_sizes:
+            raise RuntimeError(f"ShardedIndex.remove: the ranks hold {sizes} rows, expected {new_sizes} "
+                               "(did every rank pass the same ids?)")
+        removed = self.n_total - sum(sizes)
+        self._sizes = sizes
+        self.start = new_starts[self.rank]
+        self.stop = self.start + sizes[self.rank]
+        self.n_total = sum(sizes)
+        self.local.set_offset(self.start)
+        return removed
 
     def search(self, queries: torch.Tensor, k: int,
                merge: Callable = merge_topk_gpu) -> Tuple[torch.Tensor, torch.Tensor]:

@@ -113,6 +113,54 @@ class FinderIndex:
         """finder_service.py:107-216 (without the database insert)."""
         return self.report_items([src_image_path], [description], [location], [reporter], [found_at])[0]
 
+    def _saved(self, n: int) -> None:
+        self._unsaved += n
+        if self.save_every and self._unsaved >= self.save_every:
+            self.flush()
+
+    def resolve_items(self, ids: Sequence[int]) -> List[Dict]:
+        """Items handed back to their owners stop matching: their rows leave the index (in place,
+        TextSearchIndex.remove). Returns the removed records ({"id": the old row number,
+        "image_path", "description"}), in the order given. The .pt model is positional
+        (finder_service.py:93-103: row i, image_paths[i], texts[i]), so the row number of every
+        item above a removed one shifts down by the number of removed rows below it; ids handed out
+        by earlier reports must be re-read after a resolve. Uploaded image files are not deleted.
+        Counts toward `save_every` like a report does."""
+        ids = [int(i) for i in ids]
+        idx = self.index
+        for i in ids:
+            if not 0 <= i < idx.num_items:
+                raise ValueError(f"item id {i} is outside [0, {idx.num_items})")
+        if len(set(ids)) != len(ids):
+            raise ValueError("duplicate item id")
+        out = [{"id": i, "image_path": idx.image_paths[i] if i < len(idx.image_paths) else "",
+                "description": idx.texts[i] if i < len(idx.texts) else ""} for i in ids]
+        if ids:
+            idx.remove(ids)
+            self._saved(len(ids))
+        return out
+
+    def resolve_item(self, id: int) -> Dict:
+        """resolve_items for one item."""
+        return self.resolve_items([id])[0]
+
+    def update_item(self, id: int, description, location: Optional[str] = None) -> Dict:
+        """Correct an item's description: the text is re-encoded as report_items encodes it, and
+        the item's row and text are replaced in place; its id and image stay."""
+        id = int(id)
+        if not 0 <= id < self.index.num_items:
+            raise ValueError(f"item id {id} is outside [0, {self.index.num_items})")
+        if not isinstance(description, str) and location:
+            raise ValueError("a location needs a string description (token ids cannot carry it)")
+        text = _full_text(description, location) if isinstance(description, str) else description
+        tok = self.processor.token_ids(text)
+        emb = self.model.encode_ids(tok.to(self.model.device), normalize=True).to("cpu", torch.float32)
+        stored = text if isinstance(text, str) else ""
+        self.index.update([id], emb, texts=[stored])
+        self._saved(1)
+        return {"id": id, "image_path": self.index.image_paths[id] if id < len(self.index.image_paths) else "",
+                "description": stored, "location": location}
+
     def flush(self) -> None:
         """Write the index in the reference .pt format (finder_service.py:93-103)."""
         self.index.save(self.index_path)

@@ -15,6 +15,11 @@ inverse norms and the fp32 rows, streamed back to HBM without re-normalising or 
 anything (the .pt reload of search.py:29-36,68 costs torch.load + an fp32 normalise of every
 row + the fp16 rounding), bit-identical in search.
 
+.remove / .update (CosineIndex and TextSearchIndex) take rows out of the resident index or replace
+them in place (clm_index_remove / clm_index_update): an item handed back stops matching, a
+corrected description changes its row, without the read-back / reset / re-append of the whole
+index; the result is bit for bit the index built from the final rows.
+
 Scores are the exact cosines of the stored fp32 rows (fp64 arithmetic, rounded
 once): the fp16 MFMA pass only bounds the candidates (clm_index_search). Top-k
 order is (score desc, index asc); CPU torch.topk leaves exact ties in arbitrary
@@ -79,6 +84,37 @@ class CosineIndex:
         code = C.CLM_F32 if t.dtype == torch.float32 else C.CLM_F16
         C.check(C.lib().clm_index_append(self._h, C.ptr(t), code, t.shape[0], C.stream_of(self.device)),
                 "clm_index_append")
+
+    def remove(self, ids) -> int:
+        """Remove the rows with these global ids (what `search` returns; any order, a duplicate
+        counts once) in place in HBM; returns the number of rows removed. The survivors keep their
+        order: a row's new number is its old one minus the removed rows below it. ValueError for
+        an id outside the index, which is then left untouched (clm_index_remove)."""
+        t = torch.as_tensor(ids, dtype=torch.int64).reshape(-1).contiguous()
+        before = len(self)
+        C.check(C.lib().clm_index_remove(self._h, C.ptr(t) if t.numel() else None, t.numel(),
+                                         C.stream_of(self.device)), "clm_index_remove")
+        return before - len(self)
+
+    def update(self, ids, rows) -> None:
+        """Replace row ids[i] (global ids, distinct) by rows[i] in place in HBM, through the same
+        conversion as `append`: the result equals an index built with the new rows in the first
+        place. ValueError for an id outside the index or a duplicate (clm_index_update)."""
+        i = torch.as_tensor(ids, dtype=torch.int64).reshape(-1).contiguous()
+        t = torch.as_tensor(rows)
+        if t.dim() == 1:
+            t = t.unsqueeze(0)
+        if t.dim() != 2 or t.shape[1] != self.dim:
+            raise ValueError(f"rows must be [n, {self.dim}], got {tuple(t.shape)}")
+        if t.shape[0] != i.numel():
+            raise ValueError(f"{i.numel()} ids vs {t.shape[0]} rows")
+        if t.dtype not in (torch.float32, torch.float16):
+            t = t.float()
+        t = _pad_dim(t.to(self.device), self.dim_p).contiguous()
+        code = C.CLM_F32 if t.dtype == torch.float32 else C.CLM_F16
+        n = i.numel()
+        C.check(C.lib().clm_index_update(self._h, C.ptr(i) if n else None, C.ptr(t) if n else None, code, n,
+                                         C.stream_of(self.device)), "clm_index_update")
 
     def reset(self) -> None:
         C.check(C.lib().clm_index_reset(self._h))
@@ -493,6 +529,68 @@ class TextSearchIndex:
         self.image_paths.extend(image_paths)
         self.texts.extend(texts)
         self.num_items = n_new
+
+    # ------------------------------------------------------ resident mutation --
+    def _positions(self, indices) -> List[int]:
+        pos = [int(i) for i in torch.as_tensor(indices, dtype=torch.int64).reshape(-1).tolist()]
+        for p in pos:
+            if not 0 <= p < self.num_items:
+                raise ValueError(f"index {p} is outside [0, {self.num_items})")
+        return pos
+
+    def remove(self, indices) -> int:
+        """Remove the items at these positions (any order, a duplicate counts once) from the HBM
+        index, the host mirror and the metadata; returns the number removed. The items above a
+        removed one move down by one position each, keeping their order (the reference's .pt is
+        positional: row i, image_paths[i], texts[i]). image_paths / texts may be shorter than the
+        index (search.py:103-105): entries are deleted only where the list has that position. An
+        index wrapped by from_gpu_index whose host mirror was never read stays that way."""
+        gone = sorted(set(self._positions(indices)))
+        if not gone:
+            return 0
+        self._gpu.remove(gone)
+        n_new = self._n - len(gone)
+        if self._host is not None:
+            keep = torch.ones(self._n, dtype=torch.bool)
+            keep[gone] = False
+            first = gone[0]   # rows below the first removed one stay where they are
+            self._host[first: n_new] = self._host[first: self._n][keep[first:]]
+        for lst in (self.image_paths, self.texts):
+            for p in reversed(gone):
+                if p < len(lst):
+                    del lst[p]
+        self._n = self.num_items = n_new
+        return len(gone)
+
+    def update(self, indices, embeddings, image_paths: Optional[Sequence[str]] = None,
+               texts: Optional[Sequence[str]] = None) -> None:
+        """Replace the rows at these (distinct) positions by `embeddings`, re-normalised in fp32 as
+        `append` does, in HBM and in the host mirror; image_paths / texts, when given, replace the
+        items' metadata where the list is long enough to have that position."""
+        pos = self._positions(indices)
+        if len(set(pos)) != len(pos):
+            raise ValueError("duplicate index in update")
+        e = torch.as_tensor(embeddings).float().cpu()
+        if e.dim() == 1:
+            e = e.unsqueeze(0)
+        if e.dim() != 2 or e.shape[1] != self.dim:
+            raise ValueError(f"embedding dim {e.shape[-1]} != index dim {self.dim}")
+        if e.shape[0] != len(pos):
+            raise ValueError(f"{len(pos)} indices vs {e.shape[0]} embeddings")
+        for name, new in (("image_paths", image_paths), ("texts", texts)):
+            if new is not None and len(new) != len(pos):
+                raise ValueError(f"{len(pos)} indices vs {len(new)} {name}")
+        if not pos:
+            return
+        e = e / e.norm(dim=-1, keepdim=True)
+        self._gpu.update(pos, e)
+        if self._host is not None:
+            self._host[torch.tensor(pos)] = e
+        for lst, new in ((self.image_paths, image_paths), (self.texts, texts)):
+            if new is not None:
+                for p, v in zip(pos, new):
+                    if p < len(lst):
+                        lst[p] = v
 
     def save(self, path: Union[str, Path]) -> None:
         """The reference .pt format ({"embeddings": [N, D] f32, "image_paths", "texts"},

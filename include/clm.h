@@ -33,6 +33,10 @@
  *   clm_topk_merge             (new) merge of per-shard top-k lists for the
  *                              8-GPU sharded search
  *   clm_l2_normalize           v / ||v||_2 (clip_model.py:116,148; search.py:68,93)
+ *   clm_index_remove/_update   (new) the second half of the lost-and-found lifecycle: an item handed
+ *                              back stops matching, a corrected description replaces its row --
+ *                              in place in HBM instead of FinderService's reload + re-save of
+ *                              the whole index (finder_service.py:171-185)
  *   clm_index_export/_import   the index's .pt persistence (search.py:29-36,68;
  *                              finder_service.py:93-103) as a raw fp16 shard
  *   clm_resize_crop            CLIPProcessor's image resize + centre crop for inputs of any
@@ -176,6 +180,19 @@ int clm_index_reset(clm_index* idx);
  * [0, 2^62] (one index holds fewer than 2^32 rows; its searches order equal scores by the local
  * row, so results are the offset-0 results plus the offset) */
 int clm_index_set_offset(clm_index* idx, int64_t global_offset);
+/* In-place mutation of the resident index. ids (host or device) are the numbers a search returns:
+ * global ids, clm_index_set_offset's offset included. Everything is validated before anything
+ * changes: a null index, a null pointer with n > 0, a negative n, an id outside
+ * [offset, offset + size) or a dtype other than CLM_F32 / CLM_F16 is CLM_E_ARG and leaves the index
+ * bit for bit as it was; n == 0 is a no-op. Both synchronise the stream.
+ *   remove: ids in any order, a duplicate counts once. The survivors keep their order: a
+ *           survivor's new number is its old one minus the number of removed rows below it.
+ *           Rows below the first removed one are not touched; the capacity stays.
+ *   update: row ids[i] becomes rows[i] [n, dim] (host or device) through exactly the conversion of
+ *           clm_index_append (the first f32 rows start the fp32 copy); a duplicate id is CLM_E_ARG.
+ * The result equals, bit for bit, an index built by appending the final rows in order. */
+int clm_index_remove(clm_index* idx, const int64_t* ids, int64_t n_ids, void* stream);
+int clm_index_update(clm_index* idx, const int64_t* ids, const void* rows, int dtype, int64_t n, void* stream);
 /* copy rows [start, start+n) back as fp32 (host or device dst) */
 int clm_index_read(clm_index* idx, int64_t start, int64_t n, float* dst, void* stream);
 /* Shard persistence (TextSearchIndex.save_shard / load_shard; the reference persists its index
