@@ -127,6 +127,11 @@ def lib():
         "clm_attention_ex": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p]),
         "clm_layernorm": (c_int, [c_int, c_int, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_float, c_void_p,
                                   c_int64, c_void_p]),
+        "clm_text_plan": (c_int, [c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                  c_void_p, c_void_p]),
+        "clm_gemm_attn": (c_int, [c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p,
+                                  c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                  c_void_p]),
         "clm_prof_read": (c_int, [c_void_p, c_int, POINTER(ctypes.c_double), POINTER(ctypes.c_double),
                                   POINTER(c_int64)]),
     }
@@ -149,6 +154,7 @@ EXPORTED = (
     "clm_attention", "clm_attention_ex", "clm_gemm_scores16", "clm_layernorm", "clm_debug_set",
     "clm_scan16", "clm_scan16_waves", "clm_collect_ge", "clm_index_count_above", "clm_index_rank",
     "clm_index_lse", "clm_index_lse64", "clm_index_remove", "clm_index_update",
+    "clm_text_plan", "clm_gemm_attn",
 )
 CLM_EPI_STORE, CLM_EPI_GELU, CLM_EPI_RESID, CLM_EPI_SCORE = 0, 1, 2, 4
 CLM_PROF_GEMM, CLM_PROF_ATTN, CLM_PROF_LN, CLM_PROF_OTHER = 0, 1, 2, 3

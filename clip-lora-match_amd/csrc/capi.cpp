@@ -980,6 +980,45 @@ int clm_layernorm(int hip_device, int dtype, const float* src, int64_t lds, int6
   return CLM_OK;
 }
 
+// test hook: the varlen text plan alone (text_plan, k_ops.hip), as text_prologue launches it
+int clm_text_plan(int hip_device, const int32_t* ids, int B, int L, int eos, int* lens, int* offs, int* rowmap,
+                  int* tiles, int* counts, void* stream) {
+  if (B < 0 || B > 4096 || L < 1 || L > 256) return fail(CLM_E_ARG, "text_plan: 0 <= B <= 4096, 1 <= L <= 256");
+  if (B == 0) return CLM_OK;
+  if (!ids || !lens || !offs || !rowmap || !tiles || !counts) return fail(CLM_E_ARG, "text_plan: null pointer");
+  DeviceGuard g(hip_device);
+  hipError_t e = text_plan(ids, B, L, eos, lens, offs, rowmap, tiles, counts, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(CLM_E_HIP, std::string("text_plan: ") + hipGetErrorString(e));
+  return CLM_OK;
+}
+
+// test hook: the fused q/k/v projection + attention alone (k_gemm_attn.hip); the four plan pointers
+// all null: gemm_attn (B sequences of T rows), all set: gemm_attn_varlen (T = the padded length L)
+int clm_gemm_attn(int hip_device, int dtype, int flags, const void* X, int64_t ldx, const void* W, int64_t ldw,
+                  const float* bias, void* out, int64_t ldo, int B, int T, int H, int K, const int* lens,
+                  const int* offs, const int* tiles, const int* counts, void* stream) {
+  if (dtype != CLM_BF16 && dtype != CLM_F16) return fail(CLM_E_ARG, "dtype must be bf16 or f16");
+  if (flags & ~CLM_ATTN_CAUSAL) return fail(CLM_E_ARG, "unknown attention flags");
+  if (B < 0 || T < 0 || H <= 0 || H > 0x7FFFFFFF / 64) return fail(CLM_E_ARG, "bad shape");
+  const int plan = (lens != nullptr) + (offs != nullptr) + (tiles != nullptr) + (counts != nullptr);
+  if (plan != 0 && plan != 4) return fail(CLM_E_ARG, "gemm_attn: lens, offs, tiles and counts go together");
+  if (B == 0) return CLM_OK;
+  if (!X || !W || !out) return fail(CLM_E_ARG, "gemm_attn: null pointer");
+  // K % 64 == 32: rows must be readable to round_up(K, 64), as in clm_gemm
+  const int64_t kr = ((int64_t)K + 63) / 64 * 64;
+  if (K > 0 && K % 64 && (ldx < kr || ldw < kr))
+    return fail(CLM_E_ARG, "gemm_attn: K % 64 == 32 needs ldx, ldw >= round_up(K, 64)");
+  DeviceGuard g(hip_device);
+  const bool bf = dtype == CLM_BF16, cz = (flags & CLM_ATTN_CAUSAL) != 0;
+  const hipError_t e =
+      plan ? gemm_attn_varlen(bf, cz, (const u16*)X, ldx, (const u16*)W, ldw, bias, (u16*)out, ldo, B, T, H, H * 64, K,
+                              lens, offs, tiles, counts, (hipStream_t)stream)
+           : gemm_attn(bf, cz, (const u16*)X, ldx, (const u16*)W, ldw, bias, (u16*)out, ldo, B, T, H, H * 64, K,
+                       (hipStream_t)stream);
+  if (e != hipSuccess) return fail(CLM_E_HIP, std::string("gemm_attn: ") + hipGetErrorString(e));
+  return CLM_OK;
+}
+
 int clm_prof_enable(clm_ctx* ctx, int enable) {
   if (!ctx) return fail(CLM_E_ARG, "null ctx");
   DeviceGuard g(ctx->dev);

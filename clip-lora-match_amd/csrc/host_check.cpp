@@ -70,6 +70,49 @@ static void argument_checks() {
                  nullptr) == CLM_E_ARG);
   CHECK(clm_attention(0, 99, 0, nullptr, nullptr, 64, 1, 1, 1, nullptr) == CLM_E_ARG);
   CHECK(clm_layernorm(0, CLM_BF16, nullptr, 100, 4, 100, nullptr, nullptr, 1e-5f, nullptr, 100, nullptr) == CLM_E_ARG);
+  {   // the text plan and fused-attention hooks: shapes, null pointers, a partial plan
+    int one[2] = {0, 0};
+    const int32_t id1[1] = {0};
+    CHECK(clm_text_plan(0, id1, -1, 77, 1, one, one, one, one, one, nullptr) == CLM_E_ARG);
+    CHECK(clm_text_plan(0, id1, 4097, 77, 1, one, one, one, one, one, nullptr) == CLM_E_ARG);
+    CHECK(clm_text_plan(0, id1, 1, 0, 1, one, one, one, one, one, nullptr) == CLM_E_ARG);
+    CHECK(clm_text_plan(0, id1, 1, 257, 1, one, one, one, one, one, nullptr) == CLM_E_ARG);
+    CHECK(clm_text_plan(0, nullptr, 1, 77, 1, one, one, one, one, one, nullptr) == CLM_E_ARG);
+    CHECK(clm_text_plan(0, id1, 1, 77, 1, one, one, one, one, nullptr, nullptr) == CLM_E_ARG);
+    CHECK(clm_text_plan(0, nullptr, 0, 77, 1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr) == CLM_OK);
+    uint16_t x[1] = {0};
+    CHECK(clm_gemm_attn(0, 99, 0, x, 64, x, 64, nullptr, x, 64, 1, 1, 1, 64, nullptr, nullptr, nullptr, nullptr,
+                        nullptr) == CLM_E_ARG);   // dtype
+    CHECK(clm_gemm_attn(0, CLM_F16, CLM_ATTN_Q_LOG2E, x, 64, x, 64, nullptr, x, 64, 1, 1, 1, 64, nullptr, nullptr,
+                        nullptr, nullptr, nullptr) == CLM_E_ARG);   // a flag of clm_attention_ex only
+    CHECK(clm_gemm_attn(0, CLM_F16, 0, x, 64, x, 64, nullptr, x, 64, -1, 1, 1, 64, nullptr, nullptr, nullptr, nullptr,
+                        nullptr) == CLM_E_ARG);
+    CHECK(clm_gemm_attn(0, CLM_F16, 0, x, 64, x, 64, nullptr, x, 64, 1, 1, 0, 64, nullptr, nullptr, nullptr, nullptr,
+                        nullptr) == CLM_E_ARG);   // H = 0
+    CHECK(clm_gemm_attn(0, CLM_F16, 0, nullptr, 64, x, 64, nullptr, x, 64, 1, 1, 1, 64, nullptr, nullptr, nullptr,
+                        nullptr, nullptr) == CLM_E_ARG);
+    CHECK(clm_gemm_attn(0, CLM_F16, 0, x, 64, x, 64, nullptr, nullptr, 64, 1, 1, 1, 64, nullptr, nullptr, nullptr,
+                        nullptr, nullptr) == CLM_E_ARG);
+    CHECK(clm_gemm_attn(0, CLM_F16, CLM_ATTN_CAUSAL, x, 64, x, 64, nullptr, x, 64, 1, 1, 1, 64, one, one, one, nullptr,
+                        nullptr) == CLM_E_ARG);   // three of the four plan pointers
+    CHECK(clm_gemm_attn(0, CLM_F16, CLM_ATTN_CAUSAL, x, 64, x, 64, nullptr, x, 64, 1, 1, 1, 64, nullptr, nullptr,
+                        nullptr, one, nullptr) == CLM_E_ARG);
+    CHECK(clm_gemm_attn(0, CLM_F16, 0, x, 96, x, 128, nullptr, x, 64, 1, 1, 1, 96, nullptr, nullptr, nullptr, nullptr,
+                        nullptr) == CLM_E_ARG);   // K % 64 == 32 with ldx < round_up(K, 64)
+    // refused by the launcher before anything is launched: T > 128, K % 32 != 0, ldx % 8 != 0, ldo < d
+    CHECK(clm_gemm_attn(0, CLM_F16, 0, x, 64, x, 64, nullptr, x, 64, 1, 129, 1, 64, nullptr, nullptr, nullptr, nullptr,
+                        nullptr) != CLM_OK);
+    CHECK(clm_gemm_attn(0, CLM_F16, 0, x, 64, x, 64, nullptr, x, 64, 1, 1, 1, 48, nullptr, nullptr, nullptr, nullptr,
+                        nullptr) != CLM_OK);
+    CHECK(clm_gemm_attn(0, CLM_F16, 0, x, 68, x, 64, nullptr, x, 64, 1, 1, 1, 64, nullptr, nullptr, nullptr, nullptr,
+                        nullptr) != CLM_OK);
+    CHECK(clm_gemm_attn(0, CLM_F16, 0, x, 64, x, 64, nullptr, x, 60, 1, 1, 1, 64, nullptr, nullptr, nullptr, nullptr,
+                        nullptr) != CLM_OK);
+    CHECK(clm_gemm_attn(0, CLM_F16, CLM_ATTN_CAUSAL, x, 64, x, 64, nullptr, x, 64, 65536, 16, 1, 64, one, one, one,
+                        one, nullptr) != CLM_OK);   // varlen: B > 65535
+    CHECK(clm_gemm_attn(0, CLM_F16, 0, nullptr, 64, nullptr, 64, nullptr, nullptr, 64, 0, 1, 1, 64, nullptr, nullptr,
+                        nullptr, nullptr, nullptr) == CLM_OK);   // B = 0: nothing to do
+  }
   CHECK(clm_topk_merge(0, nullptr, nullptr, 1, 0, 1, 1, nullptr, nullptr, nullptr) != CLM_OK);
   CHECK(clm_l2_normalize(0, nullptr, 1, 0, nullptr) != CLM_OK);
   CHECK(clm_scan16(0, nullptr, nullptr, -1, 64, nullptr, nullptr, 1, nullptr, 1, nullptr, nullptr, 0, nullptr) ==

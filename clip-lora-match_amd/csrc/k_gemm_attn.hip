@@ -10,8 +10,12 @@
 // them (acc + bias, one v_cvt_pk), staged in LDS instead of HBM, and attended with the
 // arithmetic of attn_small_kernel (k_attn.hip): S^T = K Q^T, one exact softmax pass over <= 2
 // key tiles, O^T = V^T P^T. The output O is bit-identical to the two-kernel path
-// (tests/test_gpu_encode.py::test_fused_qkv_attention_bit_identical), and the [M, 3d] QKV
-// tensor never goes to HBM (vision: 59 MB written + read back per layer at batch 256).
+// (tests/test_gpu_encode.py::test_fused_qkv_attention_bit_identical; kernel-level, with exact-answer
+// inputs: tests/test_gpu_fused_attention.py), and the [M, 3d] QKV tensor never goes to HBM (vision:
+// 59 MB written + read back per layer at batch 256). The sequences of a tile are isolated from one
+// another as in the two-kernel path: scores of keys past a sequence's end are overwritten with -inf,
+// and their P = 0 multiplies the sequence's own last V row, never a neighbour's, so an item whose
+// q/k/v are not finite changes no other item's output.
 //
 // Main loop: the gemm_kernel structure (k_gemm.hip) at 256 x 192 x 64, 8 waves (4 x 2, 64 x 96
 // per wave), 2-stage global_load_lds ring, swapped MFMA operands (so the accumulator
@@ -43,13 +47,16 @@ static_assert(FA_BM % (8 * FA_NW) == 0 && FA_BN % (8 * FA_NW) == 0, "rows split 
 __device__ __forceinline__ int swz_s(int row, int chunk) { return chunk ^ (row & 7); }
 
 // V^T operand of O^T = V^T P^T from the staged V section (rows = tile rows): k_attn.hip's
-// v_frag_trT on absolute tile rows, clamped to the image (a clamped row only ever meets a masked
-// key, whose P is exactly 0)
-__device__ __forceinline__ u32x4 v_frag_rows(const uint8_t* sec, int kbase, int nb, int lane) {
+// v_frag_trT on absolute tile rows, clamped to `last`, the sequence's own last row. A clamped row
+// only ever meets a masked key, whose P is exactly 0 -- but 0 x Inf and 0 x NaN are NaN in the MFMA,
+// so the row must be the sequence's own: the rows after it in the tile belong to the next sequence
+// (or the next tile's first), and one non-finite item would turn its predecessor's output into NaN
+// (attn_small_kernel zero-fills V past T; tests/test_gpu_fused_attention.py holds both to it).
+__device__ __forceinline__ u32x4 v_frag_rows(const uint8_t* sec, int kbase, int nb, int lane, int last) {
   typedef short s16x4 __attribute__((ext_vector_type(4)));
   const int g = lane >> 4, i = lane & 15, q = i >> 2, p = i & 3;
   const int chunk = nb * 2 + (p >> 1);
-  const int ka = min(kbase + g * 4 + q, FA_BM - 1), kb = min(kbase + 16 + g * 4 + q, FA_BM - 1);
+  const int ka = min(kbase + g * 4 + q, last), kb = min(kbase + 16 + g * 4 + q, last);
   const uint8_t* pa = sec + ka * 128 + (swz_s(ka, chunk) << 4) + (p & 1) * 8;
   const uint8_t* pb = sec + kb * 128 + (swz_s(kb, chunk) << 4) + (p & 1) * 8;
   const s16x4 ra = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)pa);
@@ -278,7 +285,7 @@ __device__ __forceinline__ void gemm_attn_body(const FaArgs& a, int bid, int nwg
       for (int kk = 0; kk < 2; ++kk)
 #pragma unroll
         for (int nb = 0; nb < 4; ++nb)
-          o[nb] = mfma16<BF>(v_frag_rows(sV, r0 + kt * 64 + kk * 32, nb, lane), pb[kk], o[nb]);
+          o[nb] = mfma16<BF>(v_frag_rows(sV, r0 + kt * 64 + kk * 32, nb, lane, r0 + T - 1), pb[kk], o[nb]);
     }
     rs = cross_rows_reduce<false>(rs);
     if (qi < T) {

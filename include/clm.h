@@ -386,6 +386,26 @@ int clm_attention_ex(int hip_device, int dtype, int flags, const void* qkv, void
  * (TF/models/clip/modeling_clip.py:358,360 nn.LayerNorm) */
 int clm_layernorm(int hip_device, int dtype, const float* src, int64_t lds, int64_t M, int d,
                   const float* gamma, const float* beta, float eps, void* y, int64_t ldy, void* stream);
+/* the varlen text plan of ids [B, L] (device pointers): lens [B] = each caption's live rows (its
+ * pooled row + 1: the first eos, or with eos == 2 the first largest id; row 0 if there is none),
+ * offs [B + 1] = their exclusive prefix sums (offs[B] = the total), rowmap [B * L]: packed row
+ * offs[b] + p -> b * L + p (the first `total` entries are written), tiles [B]: whole captions in
+ * order, <= 256 rows per tile, tiles[t] = first caption | captions << 16 (the first counts[1]
+ * entries are written), counts [2] = {total, tiles}. 0 <= B <= 4096, 1 <= L <= 256, else CLM_E_ARG;
+ * B == 0 writes nothing. */
+int clm_text_plan(int hip_device, const int32_t* ids, int B, int L, int eos, int* lens, int* offs, int* rowmap,
+                  int* tiles, int* counts, void* stream);
+/* fused q/k/v projection + attention, T <= 128 (device pointers): out [rows, ldo >= H*64] =
+ * attention(X [rows, ldx] . W [3*H*64, ldw]^T + bias [3*H*64] or NULL), q rows of W pre-scaled by
+ * 64^-1/2; the bits of clm_gemm(CLM_EPI_STORE) followed by clm_attention. flags: CLM_ATTN_CAUSAL.
+ * K % 32 == 0 (K % 64 == 32: ldx, ldw >= round_up(K, 64), every row readable and finite that far),
+ * ldx % 8 == 0, ldw % 8 == 0, ldo % 4 == 0. lens / offs / tiles / counts all NULL: B sequences of T
+ * rows each; all set (clm_text_plan's outputs for B <= 65535 captions of padded length T): the packed
+ * live rows, sequence b at rows offs[b] .. offs[b] + lens[b]. A mixture is CLM_E_ARG; a shape the
+ * kernel does not take is an error and writes nothing. */
+int clm_gemm_attn(int hip_device, int dtype, int flags, const void* X, int64_t ldx, const void* W, int64_t ldw,
+                  const float* bias, void* out, int64_t ldo, int B, int T, int H, int K, const int* lens,
+                  const int* offs, const int* tiles, const int* counts, void* stream);
 
 /* Kernel timing by category, measured with hipEvents recorded on the launch
  * stream around every kernel of clm_encode_* while enabled (adds event

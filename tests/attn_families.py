@@ -1,5 +1,5 @@
 """Attention inputs with exactly known answers (tests/test_attn_families.py, tests/test_gpu_attention.py,
-tests/attn_mode_worker.py): qkv [B*T, 3*H*64] whose every value is exact in bf16 and in fp16, built so
+tests/attn_mode_worker.py, tests/test_gpu_fused_attention.py): qkv [B*T, 3*H*64] whose every value is exact in bf16 and in fp16, built so
 that each query's softmax sits on one key or on two equally scored keys, and an fp64 reference of
 softmax(q k^T [+ causal mask]) v per (batch, head).
 
@@ -7,7 +7,8 @@ Layout, shared by the families: B = 2, H = 3; keys are +-1 codes of 64 dims draw
 batch), redrawn until no two distinct keys agree in more than 50 dims (dot <= 36); V rows are integers
 in [-16, 16] computed from the key index with four moduli (33, 32, 31, 29) and odd multipliers, so any
 two keys of a sequence differ and neighbouring keys differ in every dim; the output has ldo = H*64 + 64
-and B*T + 8 rows, pre-filled with SENTINEL.
+and B*T + 8 rows, pre-filled with SENTINEL. make_batch cycles the two batch items into a batch of any
+size for the fused kernel, whose tiles hold many sequences.
 
   single        q_i = k_pi(i): score 64 on the intended key, N(0, 64) elsewhere; answer v_pi(i).
                 pi is a seeded permutation (every key is somebody's answer: key 0, key T-1, both sides
@@ -54,6 +55,20 @@ def cases_used():
     out += [(f, T, False, True) for T in DMA_T for f in ("single", "pair")]
     out += [(f, T, True, False) for T in CAUSAL_LONG_T for f in FAMILIES]
     return out
+
+
+# the fused q/k/v + attention kernel (k_gemm_attn.hip, tests/test_gpu_fused_attention.py): a tile holds
+# G = 256 // T sequences, which changes at 42/43, 51/52, 64/65, 85/86 and 128; the second key tile is
+# empty at 64 and holds one key at 65; the causal nkt goes from one key tile to two at query 48 -> 49
+FUSED_T = (1, 2, 15, 16, 17, 31, 32, 33, 42, 43, 48, 49, 50, 51, 52, 63, 64, 65, 77, 85, 86, 127, 128)
+FUSED_FAMILIES = (("single", False), ("pair", False), ("causal_pairs", True), ("single", True))
+
+
+def fused_batches(T):
+    """the batch sizes of the fused kernel's fixed-length tests: one sequence in the last tile
+    (G + 1) and one short of two full tiles (2 G - 1)"""
+    G = 256 // T
+    return sorted({G + 1, 2 * G - 1})
 
 
 _MODS = (33, 32, 31, 29)
@@ -159,6 +174,21 @@ def make(family, T, causal):
     return out
 
 
+@functools.lru_cache(maxsize=None)
+def make_batch(family, T, causal, nb):
+    """make()'s case as a batch of nb sequences, sequence b being item b % 2: neighbours in a batch
+    (and in a tile of the fused kernel, tests/test_gpu_fused_attention.py) carry different keys and
+    values, so a sequence offset that is one off returns another item's V row. qkv [nb*T, 3*D],
+    intended [nb, H, T, 2], expect [nb*T, D]; read-only. Goes with reference(..., nb=nb)."""
+    c = make(family, T, causal)
+    idx = np.arange(nb) % B
+    out = Case(family, T, causal, c.qkv.reshape(B, T, 3 * D)[idx].reshape(nb * T, 3 * D), c.intended[idx],
+               c.expect.reshape(B, T, D)[idx].reshape(nb * T, D))
+    for a in out[3:]:
+        a.setflags(write=False)
+    return out
+
+
 def fold_log2e(qkv):
     """(kernel input, reference input) of the CLM_ATTN_Q_LOG2E form: q times log2 e in fp32, rounded
     once to bf16; the reference sees that rounded q with log2 e divided back out in fp32."""
@@ -171,17 +201,21 @@ def fold_log2e(qkv):
     return folded, ref_in.numpy()
 
 
-def reference(qkv, T, causal, fault=None):
-    """fp64 softmax(q k^T [+ causal mask]) v -> (out [B*T, D], probabilities [B, H, T, T]).
+def reference(qkv, T, causal, fault=None, nb=B):
+    """fp64 softmax(q k^T [+ causal mask]) v -> (out [nb*T, D], probabilities [nb, H, T, T]), nb = B
+    sequences unless given (make_batch).
     `fault` plants one deliberate error in this reference (never in a kernel), for the tests that show
     the bar would catch it: "drop_last" hides key T-1, "mask_minus" / "mask_plus" shift the causal
-    mask by one key (row 0 keeps key 0), "swap_v" pairs keys 2m and 2m+1 with each other's V rows."""
-    x = np.asarray(qkv, dtype=np.float64).reshape(B, T, 3, H, HD)
+    mask by one key (row 0 keeps key 0), "swap_v" pairs keys 2m and 2m+1 with each other's V rows,
+    "next_seq" reads every sequence's V rows one sequence further on (the last one's from the first)."""
+    x = np.asarray(qkv, dtype=np.float64).reshape(nb, T, 3, H, HD)
     q, k, v = (x[:, :, i].transpose(0, 2, 1, 3) for i in range(3))   # [B, H, T, 64]
     if fault == "swap_v":
         idx = np.arange(T)
         idx[: T - (T & 1)] ^= 1
         v = v[:, :, idx]
+    if fault == "next_seq":
+        v = np.roll(v, -1, axis=0)
     s = q @ k.transpose(0, 1, 3, 2)
     ki, qi = np.arange(T)[None, :], np.arange(T)[:, None]
     vis = np.ones((T, T), bool)
@@ -196,7 +230,7 @@ def reference(qkv, T, causal, fault=None):
     s = np.where(vis, s, -np.inf)
     p = np.exp(s - s.max(-1, keepdims=True))
     p /= p.sum(-1, keepdims=True)
-    return (p @ v).transpose(0, 2, 1, 3).reshape(B * T, D), p
+    return (p @ v).transpose(0, 2, 1, 3).reshape(nb * T, D), p
 
 
 def leak(case, p):

@@ -68,6 +68,32 @@ def test_family_structure(family, causal):
                     assert (k[0: T - (T & 1): 2] == k[1::2]).all()
 
 
+@pytest.mark.parametrize("T", F.FUSED_T)
+def test_batch_helper_precondition_and_planted_sequence_shift(T):
+    """make_batch / reference(nb=...) as the fused-kernel tests use them, for every family and mask they
+    run at this T and a batch with a partial last tile: sequence b is item b % 2 bit for bit, inputs and
+    answers are exact in both 16-bit types, the leak is <= LEAK_CAP, and V rows read one sequence too
+    far -- an error planted in the reference, never in a kernel -- break the bar in every sequence
+    whose successor is the other item."""
+    nb = F.fused_batches(T)[0]
+    for family, causal in F.FUSED_FAMILIES:
+        c2, c = F.make(family, T, causal), F.make_batch(family, T, causal, nb)
+        assert c.qkv.shape == (nb * T, 3 * F.D) and c.intended.shape == (nb, F.H, T, 2)
+        for b in range(nb):
+            assert (c.qkv[b * T:(b + 1) * T] == c2.qkv[(b % 2) * T:(b % 2 + 1) * T]).all()
+            assert (c.expect[b * T:(b + 1) * T] == c2.expect[(b % 2) * T:(b % 2 + 1) * T]).all()
+        assert _exact_in_16_bits(c.qkv) and _exact_in_16_bits(c.expect)
+        ref, p = F.reference(c.qkv, T, causal, nb=nb)
+        lk = F.leak(c, p)
+        assert lk <= F.LEAK_CAP, (family, lk)
+        assert np.abs(ref - c.expect).max() <= 32 * lk + 1e-12
+        assert (ref[: 2 * T] == F.reference(c2.qkv, T, causal)[0]).all()   # nb changes no existing answer
+        bad, _ = F.reference(c.qkv, T, causal, fault="next_seq", nb=nb)
+        hit = F.violations(bad, ref, "bfloat16").reshape(nb, -1).any(1)
+        differs = np.arange(nb) % 2 != (np.arange(nb) + 1) % nb % 2
+        assert hit[differs].all() and differs.sum() >= nb - 1, (family, T)
+
+
 FAULTS = [("drop_last", "single", False), ("drop_last", "pair", False), ("drop_last", "single", True),
           ("drop_last", "pair", True), ("drop_last", "causal_pairs", True),
           ("swap_v", "single", False), ("swap_v", "pair", False), ("swap_v", "single", True),
