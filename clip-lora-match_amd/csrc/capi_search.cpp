@@ -1,0 +1,1099 @@
+// libclm C-ABI, searching the resident index: clm_index_search and its routes, exact retrieval ranks
+// and the streaming log-sum-exp, after the plumbing they share (query staging, band query blocks,
+// the exact routes' row windows, redoing a subset of the queries exactly).
+#include <algorithm>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <initializer_list>
+#include <string>
+#include <vector>
+
+#include "capi_internal.hpp"
+
+using namespace clm;
+using namespace clm::capi;
+
+namespace {
+
+// the rows the exact re-scoring reads, from row r0 on: the caller's fp32 rows where the index keeps
+// them, else its fp16 rows (which then ARE the caller's rows)
+struct ExactRows { const void* p; bool f16; };
+ExactRows exact_rows(const clm_index* x, int64_t r0 = 0) {
+  return x->rows32 ? ExactRows{x->rows32 + r0 * x->dim, false} : ExactRows{x->rows + r0 * x->dim, true};
+}
+
+// result / input copies between a workspace buffer and the caller's host or device array
+hipError_t copy_out(void* dst, const void* src, size_t bytes, hipStream_t st) {
+  return hipMemcpyAsync(dst, src, bytes, is_device_ptr(dst) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st);
+}
+hipError_t copy_in(void* dst, const void* src, size_t bytes, hipStream_t st) {
+  return hipMemcpyAsync(dst, src, bytes, is_device_ptr(src) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st);
+}
+
+// The queries of one call on the device, in x->ws: as given (qsrc: uploaded when they come from the
+// host), as fp32 rows (q32: qsrc itself for f32 queries, widened for f16 ones) with their fp64 norms
+// (qn), room for the MFMA pass's operands (q16 / qinv, filled by stage_queries_f16 on the routes
+// that run that pass), then `extra` bytes of the caller's own per-query buffers.
+struct QueryStage {
+  const void* qsrc; int q_dtype;
+  const float* q32; double* qn;
+  u16* q16; float* qinv;
+  uint8_t* extra;
+};
+int stage_queries(clm_index* x, const void* q, int q_dtype, int64_t nq, size_t extra_bytes, hipStream_t st,
+                  QueryStage* s) {
+  const int dim = (int)x->dim;
+  const bool q_dev = is_device_ptr(q), f32 = q_dtype == CLM_F32;
+  const size_t q_src_bytes = (size_t)nq * dim * (f32 ? 4 : 2);
+  Layout lay;
+  const size_t o_qsrc = q_dev ? 0 : lay.take(q_src_bytes), o_q16 = lay.take((size_t)nq * dim * 2),
+               o_qinv = lay.take((size_t)nq * 4), o_q32 = f32 ? 0 : lay.take((size_t)nq * dim * 4),
+               o_qn = lay.take((size_t)nq * 8), o_extra = lay.take(extra_bytes);
+  int r = grow(&x->ws, &x->ws_bytes, lay.total());
+  if (r) return r;
+  uint8_t* ws = (uint8_t*)x->ws;
+  const void* qsrc = q;
+  if (!q_dev) {
+    HIPCHK(hipMemcpyAsync(ws + o_qsrc, q, q_src_bytes, hipMemcpyHostToDevice, st));
+    qsrc = ws + o_qsrc;
+  }
+  const float* q32 = (const float*)qsrc;
+  if (!f32) {
+    KCHK(f16_to_f32_rows((const u16*)qsrc, nq, dim, (float*)(ws + o_q32), st));
+    q32 = (const float*)(ws + o_q32);
+  }
+  *s = QueryStage{qsrc, q_dtype, q32, (double*)(ws + o_qn), (u16*)(ws + o_q16), (float*)(ws + o_qinv), ws + o_extra};
+  KCHK(query_norms(s->q32, nq, dim, s->qn, st));
+  return CLM_OK;
+}
+
+// fp16 operands of the MFMA pass: queries normalised, then rounded
+int stage_queries_f16(const clm_index* x, const QueryStage& s, int64_t nq, hipStream_t st) {
+  KCHK(rows_to_f16(s.qsrc, s.q_dtype == CLM_F32 ? 0 : 1, nq, (int)x->dim, s.q16, s.qinv, st, 2));
+  return CLM_OK;
+}
+
+// Queries per block of a pass that streams the whole index once per block (the filter, rank and
+// log-sum-exp GEMMs): fewer, larger blocks read the index fewer times (10 M x 512 fp16 = 10 GB per
+// pass). At most $CLM_SEARCH_QB queries; with bytes_per_query > 0 the block's buffers also stay
+// within $CLM_SEARCH_WS_MB (default 8192) and a quarter of the free HBM, but hold `floor` queries at
+// least. Then balanced: the same number of blocks, equal sizes (multiples of 64 rows while that
+// stays within the cap).
+int64_t band_query_block(int64_t nq, int64_t bytes_per_query, int64_t floor) {
+  static const int64_t ws_mb = getenv("CLM_SEARCH_WS_MB") ? atoll(getenv("CLM_SEARCH_WS_MB")) : 8192;
+  // query-block cap ($CLM_SEARCH_QB, A/B): a block's fp16 queries are re-read from L2 by every
+  // index tile; with the filter GEMM on G2 tiles 2560 beats 4096 (10 k queries: 100.5 k vs 97.7 k
+  // QPS, profiles/r04_v7_search_qb_ab.txt), and the blocks are balanced (a cap of 4096 gives
+  // 10 k = 3392 + 3392 + 3216 instead of 4096 + 4096 + 1808)
+  static const int64_t qb_cap = getenv("CLM_SEARCH_QB") ? std::max<int64_t>(64, atoll(getenv("CLM_SEARCH_QB"))) : 2560;
+  int64_t nqb = std::min<int64_t>(nq, qb_cap);
+  if (bytes_per_query > 0) {
+    size_t fr = 0, tot = 0;
+    int64_t cap_b = ws_mb << 20;
+    if (hipMemGetInfo(&fr, &tot) == hipSuccess) cap_b = std::min<int64_t>(cap_b, (int64_t)(fr / 4));
+    else (void)hipGetLastError();
+    nqb = std::min<int64_t>(nqb, std::max<int64_t>(floor, cap_b / bytes_per_query));
+  }
+  const int64_t nblk = (nq + nqb - 1) / nqb;
+  const int64_t even = (nq + nblk - 1) / nblk;
+  return std::min<int64_t>(nqb, round_up(even, 64));
+}
+
+// The exact routes' row windows (rank_exact, lse_exact; windowed as search_scan(exact) is, so no
+// buffer grows with nq x N): x->ws3 holds `header` bytes of the caller's, then one [nqb, ch] window
+// of esz-byte scores within a 512 MiB budget.
+struct ExactWindows { int64_t ch, nqb; uint8_t* header; void* sc; };
+int exact_windows(clm_index* x, int64_t nq, size_t esz, size_t header, ExactWindows* w) {
+  const size_t budget = (size_t)512 << 20;
+  w->ch = round_up(std::min<int64_t>(x->n, 1 << 17), 128);
+  w->nqb = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(nq, 4096), (int64_t)(budget / ((size_t)w->ch * esz))));
+  Layout lay;
+  const size_t o_head = lay.take(header), o_sc = lay.take((size_t)w->nqb * w->ch * esz);
+  int r = grow(&x->ws3, &x->ws3_bytes, lay.total());
+  if (r) return r;
+  w->header = (uint8_t*)x->ws3 + o_head;
+  w->sc = (uint8_t*)x->ws3 + o_sc;
+  return CLM_OK;
+}
+// body(q0, nb, r0, rn, rows): queries [q0, q0 + nb) against index rows [r0, r0 + rn)
+template <class Body>
+int walk_exact_windows(const clm_index* x, const ExactWindows& w, int64_t nq, Body body) {
+  for (int64_t q0 = 0; q0 < nq; q0 += w.nqb) {
+    const int64_t nb = std::min(w.nqb, nq - q0);
+    for (int64_t r0 = 0; r0 < x->n; r0 += w.ch)
+      if (int r = body(q0, nb, r0, std::min(w.ch, x->n - r0), exact_rows(x, r0))) return r;
+  }
+  return CLM_OK;
+}
+
+// Queries `list` of a batch redone by an exact route: their rows of the `in` arrays {base, row
+// bytes} are gathered into x->ws4, body(gathered in..., out...) computes the `out` arrays' rows
+// there, and those are scattered back to rows `list` of the batch's arrays.
+struct RowArray { const void* base; int64_t row_bytes; };
+template <class Body>
+int redo_subset(clm_index* x, const std::vector<int64_t>& list, std::initializer_list<RowArray> in,
+                std::initializer_list<RowArray> out, const char* what, hipStream_t st, Body body) {
+  if (list.empty()) return CLM_OK;
+  const int64_t no = (int64_t)list.size();
+  Layout lay;
+  const size_t p_x = lay.take((size_t)no * 8);
+  std::vector<size_t> offs;
+  for (const RowArray& a : in) offs.push_back(lay.take((size_t)no * a.row_bytes));
+  for (const RowArray& a : out) offs.push_back(lay.take((size_t)no * a.row_bytes));
+  int r = grow(&x->ws4, &x->ws4_bytes, lay.total());
+  if (r) return r;
+  uint8_t* w = (uint8_t*)x->ws4;
+  std::vector<void*> g;
+  for (size_t o : offs) g.push_back(w + o);
+  int64_t* gx = (int64_t*)(w + p_x);
+  const RowArray *ai = in.begin(), *ao = out.begin();
+  void* const* go = g.data() + in.size();
+  hipError_t e = hipMemcpyAsync(gx, list.data(), (size_t)no * 8, hipMemcpyHostToDevice, st);
+  for (size_t j = 0; j < in.size() && e == hipSuccess; ++j)
+    e = gather_rows(ai[j].base, ai[j].row_bytes, gx, no, ai[j].row_bytes, g[j], ai[j].row_bytes, false, st);
+  r = e == hipSuccess ? body(g.data(), go) : fail(CLM_E_HIP, std::string(what) + " gather: " + hipGetErrorString(e));
+  for (size_t j = 0; j < out.size() && r == CLM_OK && e == hipSuccess; ++j)
+    e = gather_rows(go[j], ao[j].row_bytes, gx, no, ao[j].row_bytes, const_cast<void*>(ao[j].base), ao[j].row_bytes, true, st);
+  (void)hipStreamSynchronize(st);   // `list` (the source of gx) may go out of scope
+  if (r) return r;
+  if (e != hipSuccess) return fail(CLM_E_HIP, std::string(what) + " scatter: " + hipGetErrorString(e));
+  return CLM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// The MFMA pass scores fp16 unit-rounded operands: |fp16-pass score - exact cosine| <= 2.05e-3
+// (each side's rounding moves a cosine by <= 2u, u = 2^-11, plus fp32 accumulation of <= 1024
+// products). Every row of the exact top-k therefore has an fp16-pass score within 2 x 2.05e-3 of
+// the fp16-pass k-th best; the candidates are taken that wide (plus slack) and re-scored exactly.
+constexpr float RESCORE_MARGIN = 5e-3f;
+// ... while the fp32 accumulation error stays inside the slack: dim * 2^-24 <= 4.9e-4 for dim <= 8192
+// (every score within 1.95e-3 + 4.9e-4 of the exact cosine, twice that < RESCORE_MARGIN). Wider
+// rows are always searched by the exact scan.
+constexpr int MARGIN_MAX_DIM = 8192;
+constexpr int CAND_CAP = 2048;
+
+// Chunked scan: score chunks [nqb, ch] -- fp16 MFMA (EPI_SCORE GEMM) or exact fp64 cosines
+// (exact_scores) -- radix top-k per chunk row, merge of the chunk lists. Any k <= 1024, any N.
+static int search_scan(clm_index* x, bool exact, const u16* q16, const float* qinv, const float* q32,
+                       const double* qn, int64_t nq, int k, float* osc, int64_t* oix, hipStream_t st) {
+  const int dim = (int)x->dim;
+  const int64_t N = x->n;
+  const size_t budget = (size_t)512 << 20;
+  const int64_t max_chunks = std::max<int64_t>(1, 8192 / k);
+  int64_t ch = 1;
+  if (N > 0) {
+    ch = std::max<int64_t>((N + max_chunks - 1) / max_chunks, std::min<int64_t>(N, 1 << 17));
+    ch = round_up(ch, 128);
+  }
+  const int64_t nchunks = N > 0 ? (N + ch - 1) / ch : 0;
+  int64_t nqb = std::max<int64_t>(1, std::min<int64_t>(nq, (int64_t)(budget / ((size_t)ch * 4))));
+  nqb = std::min<int64_t>(nqb, 4096);
+  Layout lay;
+  const size_t o_sc = lay.take((size_t)nqb * ch * 4);
+  const size_t o_cs = lay.take((size_t)nqb * std::max<int64_t>(nchunks, 1) * k * 4);
+  const size_t o_ci = lay.take((size_t)nqb * std::max<int64_t>(nchunks, 1) * k * 8);
+  int r = grow(&x->ws3, &x->ws3_bytes, lay.total());
+  if (r) return r;
+  uint8_t* w = (uint8_t*)x->ws3;
+  float* sc = (float*)(w + o_sc);
+  float* cs = (float*)(w + o_cs);
+  int64_t* ci = (int64_t*)(w + o_ci);
+  for (int64_t q0 = 0; q0 < nq; q0 += nqb) {
+    const int64_t nb = std::min(nqb, nq - q0);
+    if (N == 0) {
+      KCHK(topk_rows(sc, 1, nb, 0, k, 0, osc + q0 * k, oix + q0 * k, k, st));
+      continue;
+    }
+    for (int64_t c = 0; c < nchunks; ++c) {
+      const int64_t r0 = c * ch, rn = std::min(ch, N - r0);
+      if (exact) {
+        const ExactRows er = exact_rows(x, r0);
+        KCHK(exact_scores(q32 + q0 * dim, qn + q0, nb, er.p, er.f16, rn, dim, sc, ch, st));
+      } else {
+        GemmArgs ga{};
+        ga.A = q16 + q0 * dim; ga.lda = dim; ga.W = x->rows + r0 * dim; ga.ldw = dim;
+        ga.M = (int)nb; ga.N = (int)rn; ga.K = dim; ga.out = sc; ga.ldo = ch;
+        ga.rscale = qinv + q0; ga.cscale = x->inv + r0;
+        KCHK(gemm(false, EPI_SCORE, ga, st));
+      }
+      if (nchunks == 1) {
+        KCHK(topk_rows(sc, ch, nb, rn, k, x->offset + r0, osc + q0 * k, oix + q0 * k, k, st));
+      } else {
+        KCHK(topk_rows(sc, ch, nb, rn, k, x->offset + r0, cs + c * k, ci + c * k, nchunks * k, st));
+      }
+    }
+    if (nchunks > 1) KCHK(topk_merge(cs, ci, nb, (int)nchunks, k, k, osc + q0 * k, oix + q0 * k, st));
+  }
+  return CLM_OK;
+}
+
+// Exact scan for k > 1024 (torch.topk of search.py:98 / similarity.py:57 takes any k <= N): every
+// row of a query block scored exactly into one [nqb, N] matrix, then topk_any (exact k-th key,
+// collection, LDS run sort + merge passes). The block is sized so the scores and topk_any's
+// workspace stay within a 1 GiB budget (at least one query).
+static int search_scan_large(clm_index* x, const float* q32, const double* qn, int64_t nq, int k, float* osc,
+                             int64_t* oix, hipStream_t st) {
+  const int dim = (int)x->dim;
+  const int64_t N = x->n;
+  const size_t budget = (size_t)1 << 30;
+  const size_t per_q = (size_t)std::max<int64_t>(N, 1) * 4 + topk_any_ws_bytes(1, k);
+  int64_t nqb = std::max<int64_t>(1, std::min<int64_t>(nq, (int64_t)(budget / per_q)));
+  nqb = std::min<int64_t>(nqb, 65535);
+  Layout lay;
+  const size_t o_sc = lay.take((size_t)nqb * std::max<int64_t>(N, 1) * 4);
+  const size_t o_ws = lay.take(topk_any_ws_bytes(nqb, k));
+  int r = grow(&x->ws3, &x->ws3_bytes, lay.total());
+  if (r) return r;
+  uint8_t* w = (uint8_t*)x->ws3;
+  float* sc = (float*)(w + o_sc);
+  for (int64_t q0 = 0; q0 < nq; q0 += nqb) {
+    const int64_t nb = std::min(nqb, nq - q0);
+    if (N > 0) {
+      const ExactRows er = exact_rows(x);
+      KCHK(exact_scores(q32 + q0 * dim, qn + q0, nb, er.p, er.f16, N, dim, sc, N, st));
+    }
+    KCHK(topk_any(sc, std::max<int64_t>(N, 1), nullptr, 0, nb, N, k, x->offset, osc + q0 * k, oix + q0 * k, k,
+                  w + o_ws, st));
+  }
+  return CLM_OK;
+}
+
+// The filter GEMM's cscale bounds (GemmArgs::cbound) for the current rows, computed once per row set
+// on the stream; null when the 8 bytes cannot be had. (The rank and log-sum-exp routers read them
+// to see a non-finite inverse norm.)
+static const unsigned* inv_keys_get(clm_index* x, hipStream_t st) {
+  if (!x->inv_keys && hipMalloc(&x->inv_keys, 2 * sizeof(unsigned)) != hipSuccess) {
+    (void)hipGetLastError();
+    x->inv_keys = nullptr;
+    return nullptr;
+  }
+  if (x->inv_keys_n != x->n) {
+    if (value_bounds(x->inv, x->n, x->inv_keys, st) != hipSuccess) {
+      (void)hipGetLastError();
+      return nullptr;
+    }
+    x->inv_keys_n = x->n;
+  }
+  return x->inv_keys;
+}
+// ... for the search's filter passes: null (no skip test) when $CLM_FILTER_SKIP=0 (A/B)
+static const unsigned* inv_keys_of(clm_index* x, hipStream_t st) {
+  static const bool on = !getenv("CLM_FILTER_SKIP") || atoi(getenv("CLM_FILTER_SKIP")) != 0;
+  return on ? inv_keys_get(x, st) : nullptr;
+}
+
+// Arguments of a GEMM that streams the whole index once for nb queries in M-fastest tile order
+// (EPI_FILTER / _RANK / _LSE): fp16-pass scores against theta[q], the rows that pass appended to
+// cand_i (capacity `cap` per query) and counted in cnt
+static GemmArgs index_pass(const clm_index* x, const u16* q16, const float* qinv, int64_t nb, const float* theta,
+                           int* cnt, int64_t* cand_i, int64_t cap) {
+  GemmArgs g{};
+  g.A = q16; g.lda = x->dim; g.W = x->rows; g.ldw = x->dim;
+  g.M = (int)nb; g.N = (int)x->n; g.K = (int)x->dim;
+  g.rscale = qinv; g.cscale = x->inv;
+  g.theta = theta; g.theta_ld = 1;
+  g.cnt = cnt; g.cand_i = cand_i; g.cap = (int)cap; g.base = x->offset;
+  g.m_fastest = 1;
+  return g;
+}
+
+// Whether every inverse norm of the index is finite and positive (NaN fails both tests): 0 is the
+// inverse of an infinite norm (an fp16 row holding inf), whose fp16-pass score is NaN like a zero
+// row's. *keys_out (if asked for): the device keys (inv_keys_get). Drains the stream: the callers'
+// own reads queued before it are complete too.
+static int inv_norms_finite(clm_index* x, hipStream_t st, bool* ok, const unsigned** keys_out = nullptr) {
+  unsigned hkeys[2] = {0, 0};
+  const unsigned* keys = inv_keys_get(x, st);
+  if (keys) HIPCHK(hipMemcpyAsync(hkeys, keys, sizeof(hkeys), hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  *ok = keys && key_float(hkeys[0]) > 0.f && key_float(hkeys[1]) <= 3.4028235e38f;
+  if (keys_out) *keys_out = keys;
+  return CLM_OK;
+}
+
+// Overflowed queries, wide path: their fp16 rows, inverse norms, fp32 rows, norms and filter
+// thresholds are gathered, the EPI_FILTER GEMM streams the index once more for just them with a
+// capacity of cap[j] (the first pass's count plus headroom), and rescore_wide + topk_merge pick the
+// exact top k from the whole list; results are scattered back to the queries' rows. Queries whose
+// list still exceeds its capacity are appended to `full` (the exact scan redoes them).
+static int overflow_wide(clm_index* x, const std::vector<int64_t>& qs, const std::vector<int64_t>& cap,
+                         const u16* q16, const float* qinv, const float* q32, const double* qn, const float* th,
+                         int k, float* osc, int64_t* oix, std::vector<int64_t>& full, hipStream_t st) {
+  const int dim = (int)x->dim;
+  const int64_t n = (int64_t)qs.size();
+  const ExactRows xr = exact_rows(x);
+  int64_t cap_max = 0;
+  for (int64_t c : cap) cap_max = std::max(cap_max, c);
+  cap_max = round_up(cap_max, RESCORE_WIDE_CHUNK);
+  const int64_t nch = cap_max / RESCORE_WIDE_CHUNK;
+  // queries per group: candidate lists (12 B per slot) within ~1 GB, at most 4096
+  const int64_t G = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(n, 4096), (int64_t)(1 << 30) / (cap_max * 12)));
+  Layout lay;
+  const size_t p_x = lay.take((size_t)G * 8), p_q16 = lay.take((size_t)G * dim * 2), p_qi = lay.take((size_t)G * 4),
+               p_q32 = lay.take((size_t)G * dim * 4), p_qn = lay.take((size_t)G * 8), p_th = lay.take((size_t)G * 4),
+               p_cnt = lay.take((size_t)G * 4), p_cs = lay.take((size_t)G * cap_max * 4), p_ci = lay.take((size_t)G * cap_max * 8),
+               p_ps = lay.take((size_t)G * nch * k * 4), p_pi = lay.take((size_t)G * nch * k * 8),
+               p_s = lay.take((size_t)G * k * 4), p_i = lay.take((size_t)G * k * 8);
+  if (int rg = grow(&x->ws4, &x->ws4_bytes, lay.total())) return rg;
+  uint8_t* w = (uint8_t*)x->ws4;
+  int64_t* gx = (int64_t*)(w + p_x);
+  int* cnt = (int*)(w + p_cnt);
+  std::vector<int> hcnt;
+  hipError_t e = hipSuccess;
+  for (int64_t g0 = 0; g0 < n && e == hipSuccess; g0 += G) {
+    const int64_t ng = std::min(G, n - g0);
+    e = hipMemcpyAsync(gx, qs.data() + g0, (size_t)ng * 8, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = gather_rows(q16, (int64_t)dim * 2, gx, ng, (int64_t)dim * 2, w + p_q16, (int64_t)dim * 2, false, st);
+    if (e == hipSuccess) e = gather_rows(qinv, 4, gx, ng, 4, w + p_qi, 4, false, st);
+    if (e == hipSuccess) e = gather_rows(q32, (int64_t)dim * 4, gx, ng, (int64_t)dim * 4, w + p_q32, (int64_t)dim * 4, false, st);
+    if (e == hipSuccess) e = gather_rows(qn, 8, gx, ng, 8, w + p_qn, 8, false, st);
+    if (e == hipSuccess) e = gather_rows(th, 4, gx, ng, 4, w + p_th, 4, false, st);
+    if (e == hipSuccess) e = hipMemsetAsync(cnt, 0, (size_t)ng * 4, st);
+    if (e != hipSuccess) break;
+    GemmArgs gf = index_pass(x, (const u16*)(w + p_q16), (const float*)(w + p_qi), ng, (const float*)(w + p_th), cnt,
+                             (int64_t*)(w + p_ci), cap_max);
+    gf.cand_s = (float*)(w + p_cs);
+    gf.cbound = inv_keys_of(x, st);
+    // these queries' lists overflowed: appends dominate this pass, where gemm_kernel's 256 x 256
+    // FILTER epilogue beats G2's (near-duplicate leg 73.7 k vs 66.0 k QPS,
+    // profiles/r04_v7_neardup_ab.txt)
+    static const int ocfg = getenv("CLM_GEMM_CFG") ? -1 : 1;
+    if ((e = gemm_cfg(false, EPI_FILTER, ocfg, gf, st)) != hipSuccess) break;
+    if ((e = rescore_wide((const int64_t*)(w + p_ci), cnt, cap_max, (const float*)(w + p_q32),
+                          (const double*)(w + p_qn), dim, xr.p, xr.f16, x->offset, ng, k, (float*)(w + p_ps),
+                          (int64_t*)(w + p_pi), st)) != hipSuccess) break;
+    if ((e = topk_merge((const float*)(w + p_ps), (const int64_t*)(w + p_pi), ng, (int)nch, k, k, (float*)(w + p_s),
+                        (int64_t*)(w + p_i), st)) != hipSuccess) break;
+    hcnt.resize(ng);
+    if ((e = hipMemcpyAsync(hcnt.data(), cnt, (size_t)ng * 4, hipMemcpyDeviceToHost, st)) != hipSuccess) break;
+    if ((e = hipStreamSynchronize(st)) != hipSuccess) break;
+    // scatter the complete lists' results; a list past its capacity goes to the exact scan
+    std::vector<int64_t> done;
+    std::vector<int64_t> rows_ok;
+    for (int64_t j = 0; j < ng; ++j) {
+      if (hcnt[j] > cap_max) full.push_back(qs[g0 + j]);
+      else { done.push_back(qs[g0 + j]); rows_ok.push_back(j); }
+    }
+    if (done.size() == (size_t)ng) {
+      e = gather_rows(w + p_s, (int64_t)k * 4, gx, ng, (int64_t)k * 4, osc, (int64_t)k * 4, true, st);
+      if (e == hipSuccess) e = gather_rows(w + p_i, (int64_t)k * 8, gx, ng, (int64_t)k * 8, oix, (int64_t)k * 8, true, st);
+    } else {
+      for (size_t j = 0; j < done.size() && e == hipSuccess; ++j) {
+        e = hipMemcpyAsync(osc + done[j] * k, (float*)(w + p_s) + rows_ok[j] * k, (size_t)k * 4,
+                           hipMemcpyDeviceToDevice, st);
+        if (e == hipSuccess)
+          e = hipMemcpyAsync(oix + done[j] * k, (int64_t*)(w + p_i) + rows_ok[j] * k, (size_t)k * 8,
+                             hipMemcpyDeviceToDevice, st);
+      }
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(st);   // gx is rewritten by the next group
+  }
+  (void)hipStreamSynchronize(st);
+  if (e != hipSuccess) return fail(CLM_E_HIP, std::string("overflow (wide): ") + hipGetErrorString(e));
+  return CLM_OK;
+}
+
+// Candidate lists that overflowed CAND_CAP (queries `overflow`, first-pass counts `ocount`): rebuilt
+// whole by a second filter pass (overflow_wide) or redone by the exact scan (search_bounded,
+// search_small). th: every query's filter threshold. `exact`: further queries for that one exact scan.
+static int finish_overflow(clm_index* x, const std::vector<int64_t>& overflow, const std::vector<int64_t>& ocount,
+                           const u16* q16, const float* qinv, const float* q32, const double* qn, const float* th,
+                           int k, float* osc, int64_t* oix, hipStream_t st,
+                           const std::vector<int64_t>* exact = nullptr) {
+  int r;
+  // Candidate lists beyond CAND_CAP (near-duplicate rows inside the window). Lists of up to
+  // (SORT_MAX / k) chunks are rebuilt whole by a second filter pass over just those queries and
+  // re-scored chunk-wise (overflow_wide); longer ones are redone by the exact scan, all of them in
+  // ONE scan (the index is streamed once per query block of search_scan, not once per query).
+  x->search_stats[2] += (int64_t)overflow.size();
+  std::vector<int64_t> wide, wcount, full;
+  if (exact) full = *exact;
+  for (size_t j = 0; j < overflow.size(); ++j) {
+    // headroom over the first pass's count: a different tile shape may round a score differently
+    const int64_t cap2 = ocount[j] + ocount[j] / 8 + 256;
+    if ((cap2 + RESCORE_WIDE_CHUNK - 1) / RESCORE_WIDE_CHUNK * k <= 8192) {
+      wide.push_back(overflow[j]);
+      wcount.push_back(cap2);
+    } else {
+      full.push_back(overflow[j]);
+    }
+  }
+  if (!wide.empty() && (r = overflow_wide(x, wide, wcount, q16, qinv, q32, qn, th, k, osc, oix, full, st))) return r;
+  // the rest redone by the exact scan, all of them in ONE scan; their rows of osc / oix are replaced
+  // (x->ws4: overflow_wide is done with it, it drains its stream)
+  return redo_subset(x, full, {{q32, x->dim * 4}, {qn, 8}}, {{osc, (int64_t)k * 4}, {oix, (int64_t)k * 8}}, "overflow", st,
+                     [&](void* const* in, void* const* out) -> int {
+                       return search_scan(x, true, nullptr, nullptr, (const float*)in[0], (const double*)in[1],
+                                          (int64_t)full.size(), k, (float*)out[0], (int64_t*)out[1], st);
+                     });
+}
+
+// Bounded search (large N), per block of queries:
+//  1. theta[q] <= the fp16-pass k-th best score of q:
+//     sampled (k <= 256, N >= 4S): the k-th best over a strided sample of S rows -- a subset
+//       of the index, so never above the true fp16-pass k-th best;
+//     otherwise: the chunked fp16 scan's k-th best itself.
+//  2. the EPI_FILTER GEMM streams the whole index once (M-fastest tile order: each index tile
+//     is read once and shared by all query tiles) and appends every (score, row) with
+//     score >= theta[q] - RESCORE_MARGIN to q's candidate list (capacity CAND_CAP): a
+//     superset of the exact top-k.
+//  3. rescore_select: candidates within the margin of their k-th are re-scored exactly against
+//     the caller's rows, sorted (score desc, index asc), top k written.
+//  Lists that overflowed CAND_CAP are redone by the full exact scan.
+// $CLM_KTH_RADIX=1: the sampled thresholds through topk_rows (A/B, tests)
+static const bool g_kth_radix = getenv("CLM_KTH_RADIX") && atoi(getenv("CLM_KTH_RADIX")) != 0;
+
+static int search_bounded(clm_index* x, bool sampled, int64_t S, const u16* q16, const float* qinv,
+                          const float* q32, const double* qn, int64_t nq, int k, float* osc, int64_t* oix,
+                          hipStream_t st) {
+  const int dim = (int)x->dim;
+  const int64_t N = x->n;
+  int r;
+  if (sampled && (x->samp_n != N || x->samp_S != S)) {
+    if (x->samp_cap < S) {
+      if (x->samp) (void)hipFree(x->samp);
+      if (x->samp_inv) (void)hipFree(x->samp_inv);
+      x->samp = nullptr; x->samp_inv = nullptr; x->samp_cap = 0;
+      if (hipMalloc(&x->samp, (size_t)S * dim * 2) != hipSuccess || hipMalloc(&x->samp_inv, (size_t)S * 4) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(CLM_E_OOM, "sample allocation failed");
+      }
+      x->samp_cap = S;
+    }
+    KCHK(sample_rows(x->rows, x->inv, N, dim, S, x->samp, x->samp_inv, st));
+    x->samp_n = N;
+    x->samp_S = S;
+  }
+  // the sample-score rows' stride: S (a multiple of 256 floats, 1 KB) plus 256 B, so the score
+  // GEMM's 16-row column stores do not land every row at the same power-of-two address offset
+  // ($CLM_SAMPLE_PAD floats, A/B)
+  static const int64_t spad = getenv("CLM_SAMPLE_PAD") ? atoll(getenv("CLM_SAMPLE_PAD")) : 64;
+  const int64_t ldS = S + spad;
+  // the sampled path's block is bounded by its sample-score matrix (nqb x S fp32), 256 queries at least
+  const int64_t nqb = band_query_block(nq, sampled ? ldS * 4 : 0, 256);
+  Layout lay;
+  // fp16 sample scores (rounded toward -inf: the k-th largest over them is <= the fp32 one, so
+  // the thresholds only widen) where the one-pass k-th value path runs: half the bytes of the
+  // phase's three passes ($CLM_SAMPLE_F32=1: fp32, A/B)
+  static const bool s32_env = getenv("CLM_SAMPLE_F32") && atoi(getenv("CLM_SAMPLE_F32")) != 0;
+  const bool s16 = sampled && k <= 8 && !g_kth_radix && !s32_env;
+  // ... and stored as the maxima of groups of 4 sample rows (a subset of the scores: its k-th
+  // largest is at most theirs, so θ stays a lower bound; 4x fewer bytes again). The dense-tile
+  // estimate then counts groups, times 4 (an upper bound of the scores >= θ).
+  // ($CLM_SAMPLE_GROUP=0: every score, A/B)
+  static const bool grp_env = !(getenv("CLM_SAMPLE_GROUP") && atoi(getenv("CLM_SAMPLE_GROUP")) == 0);
+  const bool sgrp = s16 && grp_env && S % 256 == 0;
+  const int64_t Sc = sgrp ? S / 4 : S;             // stored values per sample-score row
+  const int64_t ldC = sgrp ? S / 4 + 64 : ldS;     // their row stride
+  const size_t o_sc = sampled ? lay.take((size_t)nqb * ldC * (s16 ? 2 : 4)) : 0;
+  const size_t o_ts = lay.take((size_t)nqb * k * 4);
+  const size_t o_ti = lay.take((size_t)nqb * k * 8);
+  const size_t o_th = lay.take((size_t)nq * 4);   // every query's threshold (the overflow pass reuses them)
+  const size_t o_cnt = lay.take((size_t)nq * 4);   // every query's candidate count (read once, after the last block)
+  const size_t o_est = lay.take((size_t)nq * 4);
+  const size_t o_cs = lay.take((size_t)nqb * CAND_CAP * 4);
+  const size_t o_ci = lay.take((size_t)nqb * CAND_CAP * 8);
+  if ((r = grow(&x->ws2, &x->ws2_bytes, lay.total()))) return r;
+  uint8_t* w = (uint8_t*)x->ws2;
+  float* sc = (float*)(w + o_sc);
+  float* ts = (float*)(w + o_ts);
+  int64_t* ti = (int64_t*)(w + o_ti);
+  float* th = (float*)(w + o_th);
+  int* cnt = (int*)(w + o_cnt);
+  int* est = (int*)(w + o_est);
+  std::vector<int> hest;
+  float* cs = (float*)(w + o_cs);
+  int64_t* ci = (int64_t*)(w + o_ci);
+  const ExactRows xr = exact_rows(x);
+  std::vector<int> hcnt;
+  std::vector<int64_t> overflow, ocount;
+  // Phase 1, every block: the per-query thresholds (and, sampled, the estimated candidate counts)
+  // -- no host round trip between blocks
+  for (int64_t q0 = 0; q0 < nq; q0 += nqb) {
+    const int64_t nb = std::min(nqb, nq - q0);
+    if (sampled) {
+      GemmArgs ga{};
+      ga.A = q16 + q0 * dim; ga.lda = dim; ga.W = x->samp; ga.ldw = dim;
+      ga.M = (int)nb; ga.N = (int)S; ga.K = dim; ga.out = sc; ga.ldo = ldC; ga.out16 = sgrp ? 2 : s16 ? 1 : 0;
+      ga.rscale = qinv + q0; ga.cscale = x->samp_inv;
+      if (sgrp) KCHK(gemm_cfg(false, EPI_SCORE, 1, ga, st));   // config 1 (256 x 256): the group layout's tile
+      else KCHK(gemm(false, EPI_SCORE, ga, st));
+      if (s16) {
+        KCHK(kth_thresholds16((const u16*)sc, ldC, nb, Sc, k, RESCORE_MARGIN, th + q0, st));
+        KCHK(count_ge16((const u16*)sc, ldC, nb, Sc, th + q0, est + q0, st));
+      } else {
+        if (k <= 8 && !g_kth_radix) {   // one streaming pass for the k-th value alone
+          KCHK(kth_thresholds(sc, ldS, nb, S, k, RESCORE_MARGIN, th + q0, st));
+        } else {
+          KCHK(topk_rows(sc, ldS, nb, S, k, 0, ts, ti, k, st));
+          KCHK(filter_thresholds(ts, k, nb, k, RESCORE_MARGIN, th + q0, st));
+        }
+        KCHK(count_ge(sc, ldS, nb, S, th + q0, est + q0, st));
+      }
+    } else {
+      if ((r = search_scan(x, false, q16 + q0 * dim, qinv + q0, nullptr, nullptr, nb, k, ts, ti, st))) return r;
+      KCHK(filter_thresholds(ts, k, nb, k, RESCORE_MARGIN, th + q0, st));
+    }
+  }
+  // Filter tile per block, from the block's own data: when most of its queries' candidate windows
+  // hold more than CAND_CAP rows (near-duplicate rows: the sampled count above the threshold,
+  // scaled by N / S), the appends dominate the pass and gemm_kernel's 256 x 256 FILTER epilogue is
+  // the faster one; otherwise G2's 256 x 192 (same candidates either way)
+  if (sampled) {
+    hest.resize(nq);
+    HIPCHK(hipMemcpyAsync(hest.data(), est, (size_t)nq * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+  }
+  HIPCHK(hipMemsetAsync(cnt, 0, (size_t)nq * 4, st));
+  // Phase 2, every block: the filter pass and the exact re-score of its candidates
+  for (int64_t q0 = 0; q0 < nq; q0 += nqb) {
+    const int64_t nb = std::min(nqb, nq - q0);
+    bool dense = false;
+    if (sampled) {
+      int64_t over = 0;
+      for (int64_t i = 0; i < nb; ++i) over += (double)hest[q0 + i] * (sgrp ? 4.0 : 1.0) * ((double)N / (double)S) > CAND_CAP;
+      dense = 2 * over > nb;
+    }
+    GemmArgs gf = index_pass(x, q16 + q0 * dim, qinv + q0, nb, th + q0, cnt + q0, ci, CAND_CAP);
+    gf.cand_s = cs;
+    gf.cbound = inv_keys_of(x, st);
+    // never clm_debug_set / $CLM_GEMM_DEBUG (those drop epilogues: the candidate lists would be
+    // empty and the top-k wrong); the filter pass's own timing knob is $CLM_SEARCH_EPI_DEBUG,
+    // read by tools only, whose results are discarded
+    static const int search_dbg = getenv("CLM_SEARCH_EPI_DEBUG") ? (atoi(getenv("CLM_SEARCH_EPI_DEBUG")) & 3) : 0;
+    gf.debug = search_dbg;
+    static const bool cfg_forced = getenv("CLM_GEMM_CFG") != nullptr;
+    KCHK(gemm_cfg(false, EPI_FILTER, dense && !cfg_forced ? 1 : -1, gf, st));
+    x->search_stats[dense ? 5 : 4] += nb;
+    KCHK(rescore_select(cs, ci, cnt + q0, CAND_CAP, q32 + q0 * dim, qn + q0, dim, xr.p, xr.f16, x->offset,
+                        RESCORE_MARGIN, nb, k, osc + q0 * k, oix + q0 * k, st));
+  }
+  hcnt.resize(nq);
+  HIPCHK(hipMemcpyAsync(hcnt.data(), cnt, (size_t)nq * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  for (int64_t i = 0; i < nq; ++i)
+    if (hcnt[i] > CAND_CAP) {
+      overflow.push_back(i);
+      ocount.push_back(hcnt[i]);
+    }
+  x->search_stats[sampled ? 0 : 3] += nq - (int64_t)overflow.size();
+  if (overflow.empty()) return CLM_OK;
+  return finish_overflow(x, overflow, ocount, q16, qinv, q32, qn, th, k, osc, oix, st);
+}
+
+// Small query batches (nq <= 16) on a large index -- the reference's own pattern, one query per
+// search_with_embedding call (search.py:93-99, seeker_service.py:183-186). The bounded search's
+// MFMA filter pads such a batch to 256-row query tiles (>= 94 % padding) and its sampled-threshold
+// phase adds a second GEMM; here the index is streamed ONCE (scan16: fp16-pass scores of every row
+// into [N, ldq], ldq = nq rounded up to a power of two, + each 256-row chunk's maximum), then
+//  1. th[q] = (k-th largest chunk maximum of q) - RESCORE_MARGIN: k chunks whose maxima are >= the
+//     k-th largest hold k distinct rows, so it is <= the fp16-pass k-th best, a lower bound like
+//     the sampled threshold (search_bounded step 1);
+//  2. collect_ge appends every (score, row) >= th[q] (CAND_CAP per query; ~k + the rows within the
+//     margin), 4 bytes per stored score read once;
+//  3. rescore_select: exact fp64 re-score and (score desc, index asc) top k -- the same routine and
+//     bits as every other path. Lists past CAND_CAP go through finish_overflow.
+// Needs nchunk >= k (N >= 256 k) and the score matrix's offsets within one buffer descriptor.
+// from this many rows on, a small batch takes search_small by default (below it the full exact
+// scan is as fast: ~1.9 ms per query per 1 M rows at 512 dims against ~0.1 ms + launches)
+constexpr int64_t SMALL_MIN_ROWS = 65536;
+static bool search_small_fits(const clm_index* x, int64_t nq, int k) {
+  const int64_t N = x->n, dim = x->dim;
+  const int64_t nchunk = (N + 255) / 256;
+  return nq >= 1 && nq <= 16 && k >= 1 && k <= 1024 && dim >= 64 && dim <= 1024 && dim % 64 == 0 && nchunk >= k &&
+         (nq - 1) * nchunk * 4 + 4 <= 0x7FFFFFF0LL;
+}
+
+static int search_small(clm_index* x, const u16* q16, const float* qinv, const float* q32, const double* qn,
+                        int64_t nq, int k, float* osc, int64_t* oix, hipStream_t st) {
+  const int dim = (int)x->dim;
+  const int64_t N = x->n;
+  const int64_t nchunk = (N + 255) / 256;
+  int64_t ldq = 1;   // scores per index row, a power of two >= nq
+  while (ldq < nq) ldq *= 2;
+  Layout lay;
+  const size_t o_sc = lay.take((size_t)N * ldq * 4);
+  const size_t o_cm = lay.take((size_t)nq * nchunk * 4);
+  const size_t o_th = lay.take((size_t)nq * 4);
+  const size_t o_cnt = lay.take((size_t)nq * 4);
+  const size_t o_ts = lay.take((size_t)nq * k * 4);
+  const size_t o_ti = lay.take((size_t)nq * k * 8);
+  const size_t o_cs = lay.take((size_t)nq * CAND_CAP * 4);
+  const size_t o_ci = lay.take((size_t)nq * CAND_CAP * 8);
+  const int64_t W = scan16_waves(nchunk, dim);   // k <= 8: every wave's 8 largest chunk maxima
+  const int64_t ldw = W * 8;
+  const size_t o_wt = lay.take((size_t)nq * ldw * 4);
+  int r = grow(&x->ws2, &x->ws2_bytes, lay.total());
+  if (r) return r;
+  uint8_t* w = (uint8_t*)x->ws2;
+  float* sc = (float*)(w + o_sc);
+  float* cm = (float*)(w + o_cm);
+  float* th = (float*)(w + o_th);
+  int* cnt = (int*)(w + o_cnt);
+  Scan16Args a{};
+  a.rows = x->rows; a.inv = x->inv; a.N = N; a.dim = dim;
+  a.q16 = q16; a.qinv = qinv; a.nq = (int)nq;
+  a.out = sc; a.ldo = ldq; a.cmax = cm; a.nchunk = nchunk;
+  const bool wave_top = k <= 8 && !g_kth_radix && W * 8 >= k;
+  a.wtop = wave_top ? (float*)(w + o_wt) : nullptr; a.ldw = ldw;
+  KCHK(scan16(a, st));
+  if (wave_top) {   // the k-th largest of the waves' top-8 lists = the k-th largest chunk maximum
+    KCHK(kth_thresholds((const float*)(w + o_wt), ldw, nq, ldw, k, RESCORE_MARGIN, th, st));
+  } else {
+    KCHK(topk_rows(cm, nchunk, nq, nchunk, k, 0, (float*)(w + o_ts), (int64_t*)(w + o_ti), k, st));
+    KCHK(filter_thresholds((const float*)(w + o_ts), k, nq, k, RESCORE_MARGIN, th, st));
+  }
+  HIPCHK(hipMemsetAsync(cnt, 0, (size_t)nq * 4, st));
+  KCHK(collect_ge(sc, (int)ldq, (int)nq, N, th, cnt, CAND_CAP, (float*)(w + o_cs), (int64_t*)(w + o_ci), x->offset,
+                  st));
+  const ExactRows xr = exact_rows(x);
+  KCHK(rescore_select((const float*)(w + o_cs), (const int64_t*)(w + o_ci), cnt, CAND_CAP, q32, qn, dim, xr.p,
+                      xr.f16, x->offset, RESCORE_MARGIN, nq, k, osc, oix, st));
+  std::vector<int> hcnt(nq);
+  HIPCHK(hipMemcpyAsync(hcnt.data(), cnt, (size_t)nq * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  // fewer than k candidates although the index holds k rows (nchunk >= k): scores that are NaN (a
+  // zero or non-finite query; fewer than k rows with a finite norm) never pass score >= th, and
+  // no threshold describes such a top-k: the exact scan, which defines the result, serves it
+  std::vector<int64_t> overflow, ocount, degenerate;
+  for (int64_t i = 0; i < nq; ++i)
+    if (hcnt[i] > CAND_CAP) {
+      overflow.push_back(i);
+      ocount.push_back(hcnt[i]);
+    } else if (hcnt[i] < k) {
+      degenerate.push_back(i);
+    }
+  x->search_stats[6] += nq - (int64_t)overflow.size() - (int64_t)degenerate.size();
+  x->search_stats[1] += (int64_t)degenerate.size();
+  if (overflow.empty() && degenerate.empty()) return CLM_OK;
+  return finish_overflow(x, overflow, ocount, q16, qinv, q32, qn, th, k, osc, oix, st, &degenerate);
+}
+
+// Top-k by EXACT cosine (the fp32-rounded fp64 cosine of the caller's query and rows), order
+// (score desc, index asc). The reference ranks fp32 dot products of fp32-normalised rows
+// (search.py:36,68,93,96-99), i.e. the same scores to within its own fp32 summation error.
+//  * small problems (nq * N <= 2^24 dot products, or $CLM_SEARCH_FULL=1): the exact scan;
+//  * otherwise (or $CLM_SEARCH_BOUNDED=1) search_bounded, sampled when the index is large
+//    enough for sampling to pay ($CLM_SEARCH_EXACT=1 forces the chunked fp16 scan for step 1).
+int clm_index_search(clm_index* x, const void* q, int q_dtype, int64_t nq, int k, float* out_scores,
+                     int64_t* out_idx, void* stream) {
+  if (!x || nq < 0 || (nq > 0 && (!q || !out_scores || !out_idx))) return fail(CLM_E_ARG, "bad argument");
+  if (q_dtype != CLM_F32 && q_dtype != CLM_F16) return fail(CLM_E_ARG, "queries must be f32 or f16");
+  if (k < 1) return fail(CLM_E_ARG, "k must be >= 1");
+  if (k > (1 << 26)) return fail(CLM_E_ARG, "k must be <= 2^26");
+  if (nq == 0) return CLM_OK;
+  DeviceGuard g(x->dev);
+  hipStream_t st = (hipStream_t)stream;
+  const int dim = (int)x->dim;
+  const int64_t N = x->n;
+  const bool o_dev = is_device_ptr(out_scores) && is_device_ptr(out_idx);
+  Layout lay;   // the results' staging, when they go to the host
+  const size_t o_os = o_dev ? 0 : lay.take((size_t)nq * k * 4);
+  const size_t o_oi = o_dev ? 0 : lay.take((size_t)nq * k * 8);
+  QueryStage qs;
+  int r = stage_queries(x, q, q_dtype, nq, lay.total(), st, &qs);
+  if (!r) r = stage_queries_f16(x, qs, nq, st);
+  if (r) return r;
+  float* osc = o_dev ? out_scores : (float*)(qs.extra + o_os);
+  int64_t* oix = o_dev ? out_idx : (int64_t*)(qs.extra + o_oi);
+  const char* e_full = getenv("CLM_SEARCH_FULL");
+  const char* e_exact = getenv("CLM_SEARCH_EXACT");
+  const char* e_bounded = getenv("CLM_SEARCH_BOUNDED");   // tests: bounded search at any size
+  const bool force_bounded = e_bounded && atoi(e_bounded) && N > 0;
+  // small batches on a large index: one streaming pass (search_small); $CLM_SEARCH_SMALLQ=1 takes
+  // it at any size (tests), 0 never
+  const char* e_small = getenv("CLM_SEARCH_SMALLQ");
+  const int small_mode = e_small ? atoi(e_small) : -1;
+  const bool small = small_mode != 0 && k <= 1024 && N > 0 && search_small_fits(x, nq, k) &&
+                     (small_mode == 1 || (!force_bounded && !(e_full && atoi(e_full)) && !(e_exact && atoi(e_exact)) &&
+                                          N >= SMALL_MIN_ROWS));
+  if (small) {
+    r = search_small(x, qs.q16, qs.qinv, qs.q32, qs.qn, nq, k, osc, oix, st);
+  } else if (k > 1024) {
+    // any k: the exact scan over whole rows (topk_rows / the candidate lists stop at 1024)
+    r = search_scan_large(x, qs.q32, qs.qn, nq, k, osc, oix, st);
+    x->search_stats[1] += nq;
+  } else if ((e_full && atoi(e_full)) || N == 0 || dim > MARGIN_MAX_DIM ||
+             (!force_bounded && (double)nq * (double)N <= (double)(1 << 24))) {
+    r = search_scan(x, true, qs.q16, qs.qinv, qs.q32, qs.qn, nq, k, osc, oix, st);
+    x->search_stats[1] += nq;
+  } else {
+    // sample of S rows: the k-th best of the sample ranks ~k * N / S = 256 in the index, so ~256
+    // candidates per query ($CLM_SAMPLE_DIV replaces the 256: A/B only)
+    static const int64_t sdiv = getenv("CLM_SAMPLE_DIV") ? std::max<int64_t>(16, atoll(getenv("CLM_SAMPLE_DIV"))) : 256;
+    const int64_t S = round_up(std::max<int64_t>(8192, (int64_t)k * N / sdiv), 256);
+    const bool sampled = !(e_exact && atoi(e_exact)) && k <= 256 && N >= 4 * S && S <= (1 << 18);
+    r = search_bounded(x, sampled, S, qs.q16, qs.qinv, qs.q32, qs.qn, nq, k, osc, oix, st);
+  }
+  if (r) return r;
+  if (!o_dev) {
+    HIPCHK(hipMemcpyAsync(out_scores, osc, (size_t)nq * k * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(out_idx, oix, (size_t)nq * k * 8, hipMemcpyDeviceToHost, st));
+  }
+  HIPCHK(hipStreamSynchronize(st));   // workspaces are reused by the next call
+  return CLM_OK;
+}
+
+// ---- exact retrieval ranks (clm_index_rank / clm_index_count_above) ------------------------
+// above(q) = #{rows ahead of the target (t, g) in the search order}. One EPI_RANK pass decides
+// every row whose fp16-pass score s is further than RANK_MARGIN from t: RESCORE_MARGIN's comment
+// bounds |s - exact cosine| by 1.95e-3 + 4.9e-4 = 2.44e-3 for dim <= MARGIN_MAX_DIM, so
+// s > t + 2.5e-3 puts the exact score above t by more than 6e-5 and s < t - 2.5e-3 below it by
+// as much; t's own fp32 rounding and that of t +- margin (6e-8 each) are inside the 6e-5. The
+// comparison is one-sided but only one score of it (s) carries the fp16 error -- t is exact -- so
+// half of RESCORE_MARGIN, which covers two such scores, is enough.
+constexpr float RANK_MARGIN = RESCORE_MARGIN / 2;
+// band slots per query: the capacity bits of a caller's band_cap, else max(2048, N / 8); N at most
+static int64_t band_capacity(int band_cap, int64_t N) {
+  const int64_t user = band_cap > 0 ? band_cap & CLM_RANK_CAP_MASK : 0;
+  return std::min<int64_t>(N, user > 0 ? user : std::max<int64_t>(2048, N / 8));
+}
+
+// The exact route: exact scores in row windows [nqb, ch] (windowed as search_scan(exact) does:
+// no buffer grows with nq x N) and count_rank per window. q32 / qn / t / g / above: device
+// arrays of the nq queries.
+static int rank_exact(clm_index* x, const float* q32, const double* qn, const float* t, const int64_t* g,
+                      int64_t nq, int64_t* above, hipStream_t st) {
+  const int dim = (int)x->dim;
+  ExactWindows w;
+  int r = exact_windows(x, nq, 4, 0, &w);
+  if (r) return r;
+  float* sc = (float*)w.sc;
+  HIPCHK(hipMemsetAsync(above, 0, (size_t)nq * 8, st));
+  return walk_exact_windows(x, w, nq, [&](int64_t q0, int64_t nb, int64_t r0, int64_t rn, ExactRows er) -> int {
+    KCHK(exact_scores(q32 + q0 * dim, qn + q0, nb, er.p, er.f16, rn, dim, sc, w.ch, st));
+    KCHK(count_rank(sc, w.ch, nb, rn, x->offset + r0, t + q0, g + q0, above + q0, st));
+    return CLM_OK;
+  });
+}
+
+// The band route, per block of queries (blocks as search_bounded cuts them): the EPI_RANK GEMM
+// streams the index once (above32 = the rows certainly ahead, the band list = the undecided ones,
+// capacity `cap` per query), rank_rescore settles the band exactly. The band buffer (8 B per
+// slot) is what band_query_block bounds: the query block shrinks, the capacity does not. Queries
+// whose band overflowed are appended to `redo`.
+static int rank_band(clm_index* x, const unsigned* keys, const u16* q16, const float* qinv, const float* q32,
+                     const double* qn, const float* t, const int64_t* g, int64_t nq, int64_t cap, int64_t* above,
+                     std::vector<int64_t>& redo, hipStream_t st) {
+  const int dim = (int)x->dim;
+  const int64_t nqb = band_query_block(nq, cap * 8, 1);
+  Layout lay;
+  const size_t o_up = lay.take((size_t)nq * 4), o_cnt = lay.take((size_t)nq * 4), o_plan = lay.take((size_t)(nqb + 1) * 4),
+               o_band = lay.take((size_t)nqb * cap * 8);
+  int r = grow(&x->ws2, &x->ws2_bytes, lay.total());
+  if (r) return r;
+  uint8_t* w = (uint8_t*)x->ws2;
+  unsigned* above32 = (unsigned*)(w + o_up);
+  int* cnt = (int*)(w + o_cnt);
+  int64_t* band = (int64_t*)(w + o_band);
+  const ExactRows xr = exact_rows(x);
+  HIPCHK(hipMemsetAsync(above32, 0, (size_t)nq * 4, st));
+  HIPCHK(hipMemsetAsync(cnt, 0, (size_t)nq * 4, st));
+  HIPCHK(hipMemsetAsync(above, 0, (size_t)nq * 8, st));   // rank_rescore adds into it
+  for (int64_t q0 = 0; q0 < nq; q0 += nqb) {
+    const int64_t nb = std::min(nqb, nq - q0);
+    GemmArgs gr = index_pass(x, q16 + q0 * dim, qinv + q0, nb, t + q0, cnt + q0, band, cap);
+    gr.rank_margin = RANK_MARGIN;
+    gr.above = above32 + q0;
+    gr.cbound = keys;
+    KCHK(gemm_cfg(false, EPI_RANK, -1, gr, st));
+    KCHK(rank_rescore(band, cnt + q0, cap, above32 + q0, q32 + q0 * dim, qn + q0, dim, xr.p, xr.f16, x->offset,
+                      t + q0, g + q0, nb, (int*)(w + o_plan), above + q0, st));
+  }
+  std::vector<int> hcnt(nq);
+  HIPCHK(hipMemcpyAsync(hcnt.data(), cnt, (size_t)nq * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  for (int64_t i = 0; i < nq; ++i) {
+    if (hcnt[i] > cap) redo.push_back(i);
+    else x->search_stats[10] += hcnt[i];
+  }
+  return CLM_OK;
+}
+
+// Router of both entry points. tgt: the targets (rank: global row ids, validated; count_above: the
+// tie-break ids g, any value); t_in: the target scores (count_above) or null (rank: computed here).
+// A query takes the exact route when its band list overflowed or its t is NaN / infinite; the whole
+// call does when the index holds a non-finite inverse norm (a zero row scores NaN in the fp16 pass
+// as in the exact one, but only the latter is compared as the order defines), dim > MARGIN_MAX_DIM,
+// CLM_RANK_EXACT / $CLM_SEARCH_FULL=1 ask for it, or nq x N is at most the 2^24 dot products below
+// which clm_index_search takes its exact scan too (CLM_RANK_BAND / $CLM_SEARCH_BOUNDED=1: the band
+// route at any size, tests). The counts do not depend on the route: both compare exact_cos scores.
+static int rank_run(clm_index* x, const void* q, int q_dtype, int64_t nq, const float* t_in, const int64_t* tgt,
+                    int64_t* out_i, float* out_s, int band_cap, void* stream) {
+  const bool is_rank = t_in == nullptr;
+  if (q_dtype != CLM_F32 && q_dtype != CLM_F16) return fail(CLM_E_ARG, "queries must be f32 or f16");
+  if (x->n == 0) return fail(CLM_E_ARG, "the index is empty");
+  if (nq == 0) return CLM_OK;
+  DeviceGuard guard(x->dev);
+  hipStream_t st = (hipStream_t)stream;
+  const int dim = (int)x->dim;
+  const int64_t N = x->n;
+  std::vector<int64_t> htgt(nq);
+  if (is_device_ptr(tgt)) {
+    HIPCHK(hipMemcpyAsync(htgt.data(), tgt, (size_t)nq * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+  } else {
+    std::memcpy(htgt.data(), tgt, (size_t)nq * 8);
+  }
+  if (is_rank)
+    for (int64_t i = 0; i < nq; ++i)
+      if (htgt[i] < x->offset || htgt[i] - x->offset >= N)
+        return fail(CLM_E_ARG, "target " + std::to_string(htgt[i]) + " of query " + std::to_string(i) +
+                                   " is outside the index [" + std::to_string(x->offset) + ", " +
+                                   std::to_string(x->offset + N) + ")");
+  Layout lay;
+  const size_t o_t = lay.take((size_t)nq * 4), o_g = lay.take((size_t)nq * 8), o_ab = lay.take((size_t)nq * 8),
+               o_rk = lay.take((size_t)nq * 8);
+  QueryStage qs;
+  int r = stage_queries(x, q, q_dtype, nq, lay.total(), st, &qs);
+  if (r) return r;
+  const float* q32 = qs.q32;
+  const double* qn = qs.qn;
+  float* t = (float*)(qs.extra + o_t);
+  int64_t* g = (int64_t*)(qs.extra + o_g);
+  int64_t* above = (int64_t*)(qs.extra + o_ab);
+  int64_t* rank = (int64_t*)(qs.extra + o_rk);
+  const ExactRows xr = exact_rows(x);
+  HIPCHK(hipMemcpyAsync(g, htgt.data(), (size_t)nq * 8, hipMemcpyHostToDevice, st));
+  if (is_rank) KCHK(target_scores(q32, qn, nq, dim, xr.p, xr.f16, x->offset, g, t, st));
+  else HIPCHK(copy_in(t, t_in, (size_t)nq * 4, st));
+  std::vector<float> ht(nq);
+  HIPCHK(hipMemcpyAsync(ht.data(), t, (size_t)nq * 4, hipMemcpyDeviceToHost, st));
+  const unsigned* keys = nullptr;
+  bool inv_ok = false;
+  if ((r = inv_norms_finite(x, st, &inv_ok, &keys))) return r;
+  const int flags = band_cap > 0 ? band_cap & (CLM_RANK_EXACT | CLM_RANK_BAND) : 0;
+  const char* e_full = getenv("CLM_SEARCH_FULL");
+  const char* e_bounded = getenv("CLM_SEARCH_BOUNDED");
+  const bool force_exact = (flags & CLM_RANK_EXACT) || (e_full && atoi(e_full));
+  const bool force_band = (flags & CLM_RANK_BAND) || (e_bounded && atoi(e_bounded));
+  const bool all_exact = force_exact || !inv_ok || dim > MARGIN_MAX_DIM || N > 0x7FFFFFFF ||
+                         (!force_band && (double)nq * (double)N <= (double)(1 << 24));
+  if (all_exact) {
+    if ((r = rank_exact(x, q32, qn, t, g, nq, above, st))) return r;
+    x->search_stats[8] += nq;
+  } else {
+    if ((r = stage_queries_f16(x, qs, nq, st))) return r;
+    const int64_t cap = band_capacity(band_cap, N);
+    std::vector<int64_t> redo;
+    if ((r = rank_band(x, keys, qs.q16, qs.qinv, q32, qn, t, g, nq, cap, above, redo, st))) return r;
+    x->search_stats[9] += (int64_t)redo.size();
+    std::vector<char> listed(nq, 0);
+    for (int64_t i : redo) listed[i] = 1;
+    for (int64_t i = 0; i < nq; ++i)
+      if (!listed[i] && !(std::fabs(ht[i]) <= 3.4028235e38f)) redo.push_back(i);   // NaN or infinite t
+    x->search_stats[7] += nq - (int64_t)redo.size();
+    x->search_stats[8] += (int64_t)redo.size();
+    // their queries, norms and targets gathered, one exact pass, counts scattered back
+    r = redo_subset(x, redo, {{q32, (int64_t)dim * 4}, {qn, 8}, {t, 4}, {g, 8}}, {{above, 8}}, "rank", st,
+                    [&](void* const* in, void* const* out) -> int {
+                      return rank_exact(x, (const float*)in[0], (const double*)in[1], (const float*)in[2],
+                                        (const int64_t*)in[3], (int64_t)redo.size(), (int64_t*)out[0], st);
+                    });
+    if (r) return r;
+  }
+  const int64_t* res = above;
+  if (is_rank) {
+    KCHK(rank_from_above(above, nq, rank, st));
+    res = rank;
+  }
+  HIPCHK(copy_out(out_i, res, (size_t)nq * 8, st));
+  if (out_s) HIPCHK(copy_out(out_s, t, (size_t)nq * 4, st));
+  HIPCHK(hipStreamSynchronize(st));   // workspaces are reused by the next call
+  return CLM_OK;
+}
+
+int clm_index_count_above(clm_index* x, const void* q, int q_dtype, int64_t nq, const float* t_score,
+                          const int64_t* t_index, int64_t* out_above, int band_cap, void* stream) {
+  if (!x || nq < 0 || (nq > 0 && (!q || !t_score || !t_index || !out_above))) return fail(CLM_E_ARG, "bad argument");
+  return rank_run(x, q, q_dtype, nq, t_score, t_index, out_above, nullptr, band_cap, stream);
+}
+
+int clm_index_rank(clm_index* x, const void* q, int q_dtype, int64_t nq, const int64_t* target, int64_t* out_rank,
+                   float* out_score, int band_cap, void* stream) {
+  if (!x || nq < 0 || (nq > 0 && (!q || !target || !out_rank))) return fail(CLM_E_ARG, "bad argument");
+  return rank_run(x, q, q_dtype, nq, nullptr, target, out_rank, out_score, band_cap, stream);
+}
+
+// ---- streaming log-sum-exp (clm_index_lse) --------------------------------------------------
+// lse(q) = log sum_j exp(scale * s_j) over the exact scores, in fp64. The fast route's certified
+// bound rests on E >= |fp16-pass score - s_j|: RESCORE_MARGIN's comment gives 1.95e-3 + 4.9e-4 for
+// dim <= MARGIN_MAX_DIM against the exact cosine; 1e-6 more covers the fp32 roundings of s_j itself
+// and of the fp16-pass score's two scale products (6e-8 each).
+constexpr double LSE_E = 1.95e-3 + 4.9e-4 + 1e-6;
+
+// The exact route: exact scores in rank_exact's row windows, folded into a running (maximum, sum)
+// per query. A query's result depends on the index alone, not on nq. q32 / qn / lse / err: device
+// arrays of the nq queries (err may be null). f64: the reference route of clm_index_lse64, the same
+// windows of unrounded fp64 cosines; pair[q] (device, or null) takes the cosine of row target[q].
+static int lse_exact(clm_index* x, const float* q32, const double* qn, int64_t nq, double scale, double* lse,
+                     float* err, hipStream_t st, bool f64 = false, const int64_t* target = nullptr,
+                     double* pair = nullptr) {
+  const int dim = (int)x->dim;
+  ExactWindows w;
+  int r = exact_windows(x, nq, f64 ? 8 : 4, (size_t)nq * sizeof(double2), &w);
+  if (r) return r;
+  double2* state = (double2*)w.header;
+  void* sc = w.sc;
+  const int64_t ch = w.ch;
+  KCHK(lse_fold_init(state, nq, st));
+  r = walk_exact_windows(x, w, nq, [&](int64_t q0, int64_t nb, int64_t r0, int64_t rn, ExactRows er) -> int {
+    if (f64) {
+      KCHK(lse_scores64(q32 + q0 * dim, qn + q0, nb, er.p, er.f16, rn, dim, (double*)sc, ch, st));
+      KCHK(lse_fold64((const double*)sc, ch, nb, rn, scale, state + q0, target ? target + q0 : nullptr, x->offset,
+                      r0, pair ? pair + q0 : nullptr, st));
+    } else {
+      KCHK(exact_scores(q32 + q0 * dim, qn + q0, nb, er.p, er.f16, rn, dim, (float*)sc, ch, st));
+      KCHK(lse_fold((const float*)sc, ch, nb, rn, scale, state + q0, st));
+    }
+    return CLM_OK;
+  });
+  if (r) return r;
+  KCHK(lse_fold_finish(state, nq, scale, lse, err, st));
+  return CLM_OK;
+}
+
+// The fast route, per block of queries (rank_band's blocks): the EPI_LSE GEMM streams the index
+// once (band list = the rows at or above theta - RANK_MARGIN, slab = the tail partials), then
+// lse_band_scores re-scores the band and lse_finish combines. Band (8 + 4 B per slot) and slab
+// (4 B per slot) are what band_query_block bounds: the query block shrinks. redo[q] = 1 (device)
+// marks the queries left to the exact route; `overflowed` counts those whose band exceeded `cap`.
+static int lse_band(clm_index* x, const u16* q16, const float* qinv, const float* q32, const double* qn,
+                    const float* theta, int64_t nq, int64_t cap, double scale, double* lse, float* err, int* redo,
+                    std::vector<int64_t>& redo_list, int64_t& overflowed, hipStream_t st) {
+  const int dim = (int)x->dim;
+  const int64_t N = x->n;
+  const int64_t slots = lse_slots(N);
+  const int64_t nqb = band_query_block(nq, cap * 12 + slots * 4, 1);
+  Layout lay;
+  const size_t o_cnt = lay.take((size_t)nq * 4), o_plan = lay.take((size_t)(nqb + 1) * 4),
+               o_band = lay.take((size_t)nqb * cap * 8), o_bs = lay.take((size_t)nqb * cap * 4),
+               o_slab = lay.take((size_t)nqb * slots * 4);
+  int r = grow(&x->ws2, &x->ws2_bytes, lay.total());
+  if (r) return r;
+  uint8_t* w = (uint8_t*)x->ws2;
+  int* cnt = (int*)(w + o_cnt);
+  int64_t* band = (int64_t*)(w + o_band);
+  float* band_s = (float*)(w + o_bs);
+  float* slab = (float*)(w + o_slab);
+  const ExactRows xr = exact_rows(x);
+  HIPCHK(hipMemsetAsync(cnt, 0, (size_t)nq * 4, st));
+  HIPCHK(hipMemsetAsync(redo, 0, (size_t)nq * 4, st));
+  for (int64_t q0 = 0; q0 < nq; q0 += nqb) {
+    const int64_t nb = std::min(nqb, nq - q0);
+    HIPCHK(hipMemsetAsync(slab, 0, (size_t)nb * slots * 4, st));   // the slots the chosen tiles do not use
+    GemmArgs gr = index_pass(x, q16 + q0 * dim, qinv + q0, nb, theta + q0, cnt + q0, band, cap);
+    gr.rank_margin = RANK_MARGIN;
+    gr.lse_part = slab; gr.lse_ld = slots; gr.lse_c = (float)(scale * 1.4426950408889634);
+    KCHK(gemm_cfg(false, EPI_LSE, -1, gr, st));
+    KCHK(lse_band_scores(band, cnt + q0, cap, q32 + q0 * dim, qn + q0, dim, xr.p, xr.f16, x->offset, nb,
+                         (int*)(w + o_plan), band_s, st));
+    KCHK(lse_finish(band_s, cnt + q0, cap, slab, slots, theta + q0, scale, LSE_E, N, nb, lse + q0, err + q0,
+                    redo + q0, st));
+  }
+  std::vector<int> hcnt(nq), hredo(nq);
+  HIPCHK(hipMemcpyAsync(hcnt.data(), cnt, (size_t)nq * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(hredo.data(), redo, (size_t)nq * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  for (int64_t i = 0; i < nq; ++i) {
+    if (hredo[i]) redo_list.push_back(i);
+    if (hcnt[i] > cap) ++overflowed;
+  }
+  return CLM_OK;
+}
+
+int clm_index_lse(clm_index* x, const void* q, int q_dtype, int64_t nq, double scale, const float* head_floor,
+                  double* out_lse, float* out_err, int band_cap, void* stream) {
+  if (!x || nq < 0 || (nq > 0 && (!q || !out_lse))) return fail(CLM_E_ARG, "bad argument");
+  if (q_dtype != CLM_F32 && q_dtype != CLM_F16) return fail(CLM_E_ARG, "queries must be f32 or f16");
+  if (!(scale > 0.0 && scale <= 1.7976931348623157e308)) return fail(CLM_E_ARG, "scale must be finite and positive");
+  if (x->n == 0) return fail(CLM_E_ARG, "the index is empty");
+  if (nq == 0) return CLM_OK;
+  DeviceGuard guard(x->dev);
+  hipStream_t st = (hipStream_t)stream;
+  const int dim = (int)x->dim;
+  const int64_t N = x->n;
+  Layout lay;
+  const size_t o_th = lay.take((size_t)nq * 4), o_lse = lay.take((size_t)nq * 8), o_err = lay.take((size_t)nq * 4),
+               o_redo = lay.take((size_t)nq * 4);
+  QueryStage qs;
+  int r = stage_queries(x, q, q_dtype, nq, lay.total(), st, &qs);
+  if (r) return r;
+  const float* q32 = qs.q32;
+  const double* qn = qs.qn;
+  float* theta = (float*)(qs.extra + o_th);
+  double* lse = (double*)(qs.extra + o_lse);
+  float* err = (float*)(qs.extra + o_err);
+  int* redo = (int*)(qs.extra + o_redo);
+  // as rank_run: every inverse norm finite and positive, or the whole call is exact
+  bool inv_ok = false;
+  if ((r = inv_norms_finite(x, st, &inv_ok))) return r;
+  const int flags = band_cap > 0 ? band_cap & (CLM_LSE_EXACT | CLM_LSE_FAST) : 0;
+  const char* e_full = getenv("CLM_SEARCH_FULL");
+  const bool force_exact = (flags & CLM_LSE_EXACT) || (e_full && atoi(e_full));
+  const bool force_fast = (flags & CLM_LSE_FAST) != 0;
+  const bool all_exact = force_exact || !inv_ok || dim > MARGIN_MAX_DIM || N > 0x7FFFFFFF || !head_floor ||
+                         (!force_fast && (double)nq * (double)N <= (double)(1 << 24));
+  if (all_exact) {
+    if ((r = lse_exact(x, q32, qn, nq, scale, lse, err, st))) return r;
+    x->search_stats[12] += nq;
+  } else {
+    HIPCHK(copy_in(theta, head_floor, (size_t)nq * 4, st));
+    if ((r = stage_queries_f16(x, qs, nq, st))) return r;
+    const int64_t cap = band_capacity(band_cap, N);
+    std::vector<int64_t> todo;
+    int64_t overflowed = 0;
+    if ((r = lse_band(x, qs.q16, qs.qinv, q32, qn, theta, nq, cap, scale, lse, err, redo, todo, overflowed, st))) return r;
+    x->search_stats[13] += overflowed;
+    x->search_stats[11] += nq - (int64_t)todo.size();
+    x->search_stats[12] += (int64_t)todo.size();
+    // their queries and norms gathered, one exact pass, results scattered back
+    r = redo_subset(x, todo, {{q32, (int64_t)dim * 4}, {qn, 8}}, {{lse, 8}, {err, 4}}, "lse", st,
+                    [&](void* const* in, void* const* out) -> int {
+                      return lse_exact(x, (const float*)in[0], (const double*)in[1], (int64_t)todo.size(), scale,
+                                       (double*)out[0], (float*)out[1], st);
+                    });
+    if (r) return r;
+  }
+  HIPCHK(copy_out(out_lse, lse, (size_t)nq * 8, st));
+  if (out_err) HIPCHK(copy_out(out_err, err, (size_t)nq * 4, st));
+  HIPCHK(hipStreamSynchronize(st));   // workspaces are reused by the next call
+  return CLM_OK;
+}
+
+// The reference route: lse_exact on the unrounded fp64 cosines. Nothing here is rounded to fp32, so
+// a loss built from out_lse and out_pair is the fp64 loss of the same rows to fp64 rounding.
+int clm_index_lse64(clm_index* x, const void* q, int q_dtype, int64_t nq, double scale, const int64_t* target,
+                    double* out_lse, double* out_pair, void* stream) {
+  if (!x || nq < 0 || (nq > 0 && (!q || !out_lse || (out_pair && !target)))) return fail(CLM_E_ARG, "bad argument");
+  if (q_dtype != CLM_F32 && q_dtype != CLM_F16) return fail(CLM_E_ARG, "queries must be f32 or f16");
+  if (!(scale > 0.0 && scale <= 1.7976931348623157e308)) return fail(CLM_E_ARG, "scale must be finite and positive");
+  if (x->n == 0) return fail(CLM_E_ARG, "the index is empty");
+  if (nq == 0) return CLM_OK;
+  DeviceGuard guard(x->dev);
+  hipStream_t st = (hipStream_t)stream;
+  Layout lay;
+  const size_t o_lse = lay.take((size_t)nq * 8), o_pair = lay.take((size_t)nq * 8), o_tg = lay.take((size_t)nq * 8);
+  QueryStage qs;
+  int r = stage_queries(x, q, q_dtype, nq, lay.total(), st, &qs);
+  if (r) return r;
+  double* lse = (double*)(qs.extra + o_lse);
+  double* pair = out_pair ? (double*)(qs.extra + o_pair) : nullptr;
+  int64_t* tg = pair ? (int64_t*)(qs.extra + o_tg) : nullptr;
+  if (pair) {
+    HIPCHK(copy_in(tg, target, (size_t)nq * 8, st));
+    HIPCHK(hipMemsetAsync(pair, 0xFF, (size_t)nq * 8, st));   // NaN: a target outside the index keeps it
+  }
+  if ((r = lse_exact(x, qs.q32, qs.qn, nq, scale, lse, nullptr, st, true, tg, pair))) return r;
+  x->search_stats[12] += nq;
+  HIPCHK(copy_out(out_lse, lse, (size_t)nq * 8, st));
+  if (pair) HIPCHK(copy_out(out_pair, pair, (size_t)nq * 8, st));
+  HIPCHK(hipStreamSynchronize(st));   // workspaces are reused by the next call
+  return CLM_OK;
+}
+
+}  // extern "C"

@@ -9,7 +9,7 @@
 // Only the window the crop keeps is computed: the S kept columns of pass 1 over the source rows the
 // S kept rows need, then pass 2 for the S x S crop. Each output pixel depends only on its taps, so
 // the crop equals PIL's full resize followed by transformers' centre crop bit for bit.
-// Tap tables are built on the host (capi.cpp, double precision in PIL's operation order).
+// Tap tables are built on the host (capi_ops.cpp, double precision in PIL's operation order).
 #include <algorithm>
 
 #include "kernels.hpp"

@@ -974,7 +974,7 @@ namespace {
 //  * cmax[q][chunk] = the largest fp16-pass score of the chunk (NaN scores ignored, rows past N
 //    -inf). The k-th largest chunk maximum is at most the k-th largest score of the whole index
 //    (k chunks whose maxima reach it hold k distinct rows), so th = that - margin bounds the
-//    candidates exactly as the sampled threshold does (capi.cpp search_small).
+//    candidates exactly as the sampled threshold does (capi_search.cpp search_small).
 // Counted vmcnt: in the steady state the DMA of block i is older than one score store and D - 2
 // (DMA + store) groups; the first and last D - 1 blocks, and the extra chunk-maximum stores, only
 // ever make the wait longer (vmcnt(0) there).

@@ -165,7 +165,7 @@ int clm_encode_pair(clm_ctx* ctx, const void* pixels, int pix_layout, int n_img,
 int clm_pair_path(const clm_ctx* ctx);
 
 /* GPU-resident cosine index (dim % 64 == 0, <= 65536; rows wider than 8192 are always searched by
- * the exact scan, MARGIN_MAX_DIM in capi.cpp). Scores are the EXACT cosine of the
+ * the exact scan, MARGIN_MAX_DIM in capi_search.cpp). Scores are the EXACT cosine of the
  * caller's query and rows (fp64 arithmetic, rounded once to fp32): an fp16 MFMA pass bounds the
  * candidates, which are then re-scored against the rows as given. */
 int clm_index_create(int hip_device, int64_t capacity, int dim, clm_index** out);

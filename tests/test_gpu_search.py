@@ -484,6 +484,91 @@ def test_fuse_queries_c_abi_host_pointers():
         C.check(C.lib().clm_fuse_queries(0, C.ptr(dev), 1.0, None, 0.0, 9, 512, vp(out), None))
 
 
+def test_query_sources_c_abi_bit_identical(monkeypatch):
+    """The index entry points take their queries as host or device memory, f32 or f16. With query
+    values that fp16 holds exactly the four sources are the same numbers, and search (default route
+    and the bounded one), rank (exact and band route), the exact log-sum-exp and lse64 must return
+    the same bits for all four. The fast log-sum-exp normalises f32 queries before it rounds them and
+    f16 queries after, so its fp16-pass operands differ by dtype: there host and device of one dtype
+    are bit-identical, and the two dtypes are each within their returned bound of the exact result,
+    hence within the sum of the two bounds of each other."""
+    import ctypes
+
+    from clip_lora_match_amd import _capi as C
+    N, dim, nq, k, off, scale = 300, 64, 3, 5, 1000, 20.0
+    rows = syn.gaussian_rows(N, dim, 41).astype(np.float32)
+    rows[17] = rows[17].astype(np.float16).astype(np.float32)
+    q32 = syn.gaussian_rows(nq, dim, 42).astype(np.float16).astype(np.float32)
+    q32[1] = rows[17]   # a query equal to an index row
+    q16 = q32.astype(np.float16)
+    assert np.array_equal(q16.astype(np.float32), q32)
+    d32, d16 = torch.from_numpy(q32).cuda(), torch.from_numpy(q16).cuda()
+    vp = lambda a: ctypes.c_void_p(a.ctypes.data)  # noqa: E731
+    sources = [(vp(q32), C.CLM_F32), (C.ptr(d32), C.CLM_F32), (vp(q16), C.CLM_F16), (C.ptr(d16), C.CLM_F16)]
+    target = np.array([off + 3, off + 17, off + N - 1], np.int64)
+    L = C.lib()
+    h = ctypes.c_void_p()
+    C.check(L.clm_index_create(0, N, dim, ctypes.byref(h)))
+    try:
+        C.check(L.clm_index_append(h, vp(rows), C.CLM_F32, N, None))
+        C.check(L.clm_index_set_offset(h, off))
+
+        def search(q, dt):
+            s, i = np.empty((nq, k), np.float32), np.empty((nq, k), np.int64)
+            C.check(L.clm_index_search(h, q, dt, nq, k, vp(s), vp(i), None))
+            return s, i
+
+        def rank(flag):
+            def run(q, dt):
+                r, s = np.empty(nq, np.int64), np.empty(nq, np.float32)
+                C.check(L.clm_index_rank(h, q, dt, nq, vp(target), vp(r), vp(s), flag, None))
+                return r, s
+            return run
+
+        def lse(flag, floor):
+            def run(q, dt):
+                v, e = np.empty(nq, np.float64), np.empty(nq, np.float32)
+                C.check(L.clm_index_lse(h, q, dt, nq, scale, vp(floor) if floor is not None else None, vp(v), vp(e),
+                                        flag, None))
+                return v, e
+            return run
+
+        def lse64(q, dt):
+            v, p = np.empty(nq, np.float64), np.empty(nq, np.float64)
+            C.check(L.clm_index_lse64(h, q, dt, nq, scale, vp(target), vp(v), vp(p), None))
+            return v, p
+
+        def four(fn):
+            return [fn(q, dt) for q, dt in sources]
+
+        def same_bits(a, b):
+            return all(x.tobytes() == y.tobytes() for x, y in zip(a, b))
+
+        base = search(*sources[0])
+        assert base[1][1, 0] == off + 17 and base[0][1, 0] == 1.0   # the query that is a row finds it
+        ref = S.cosine_scores(q32.astype(np.float64), rows.astype(np.float64))
+        for j in range(nq):
+            assert S.same_topk_up_to_ties(base[1][j] - off, S.topk(ref, k)[1][j], ref[j], 2e-6)
+        calls = {"search": search, "rank exact": rank(C.CLM_RANK_EXACT), "rank band": rank(C.CLM_RANK_BAND),
+                 "lse exact": lse(C.CLM_LSE_EXACT, None), "lse64": lse64}
+        for name, fn in calls.items():
+            got = four(fn)
+            assert all(same_bits(got[0], g) for g in got[1:]), name
+        with monkeypatch.context() as m:
+            m.setenv("CLM_SEARCH_BOUNDED", "1")
+            got = four(search)
+        assert all(same_bits(base, g) for g in got), "bounded search"
+        floor = np.ascontiguousarray(base[0][:, k - 1])   # the k-th exact score of each query
+        h32, d32r, h16, d16r = four(lse(C.CLM_LSE_FAST, floor))
+        assert same_bits(h32, d32r) and same_bits(h16, d16r)
+        assert np.all(np.abs(h32[0] - h16[0]) <= h32[1].astype(np.float64) + h16[1].astype(np.float64))
+        exact = lse(C.CLM_LSE_EXACT, None)(*sources[0])[0]
+        for v, e in (h32, h16):
+            assert np.all(np.abs(v - exact) <= e)
+    finally:
+        C.check(L.clm_index_destroy(h))
+
+
 def test_build_query_embedding_and_search_items(tmp_path):
     from PIL import Image
 

@@ -173,7 +173,7 @@ def _f16_down(v):
 
 
 def test_sampled_threshold_stays_a_lower_bound():
-    """The bounded search's sampled θ (capi.cpp search_bounded) is the k-th largest of the stored
+    """The bounded search's sampled θ (capi_search.cpp search_bounded) is the k-th largest of the stored
     sample scores minus the margin; round 5 stores them as fp16 rounded toward -inf and as maxima
     of groups of 4 sample rows. Both only lower the k-th largest: f16_down(v) <= v for every v
     (ties, subnormals, signs, infinities), and the k-th largest of group maxima (a subset of the
