@@ -132,6 +132,20 @@ def lib():
         "clm_gemm_attn": (c_int, [c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p,
                                   c_int64, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                   c_void_p]),
+        "clm_layernorm_ex": (c_int, [c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int,
+                                     c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p,
+                                     c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
+        "clm_gemm_ex": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int,
+                                c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int, c_void_p,
+                                c_void_p]),
+        "clm_patchify": (c_int, [c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int,
+                                 c_void_p]),
+        "clm_write_cls": (c_int, [c_int, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+        "clm_gather_pooled": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int, c_void_p,
+                                      c_int, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+        "clm_pool_project": (c_int, [c_int, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_int, c_void_p,
+                                     c_void_p, c_float, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p,
+                                     c_void_p]),
         "clm_prof_read": (c_int, [c_void_p, c_int, POINTER(ctypes.c_double), POINTER(ctypes.c_double),
                                   POINTER(c_int64)]),
     }
@@ -155,8 +169,10 @@ EXPORTED = (
     "clm_scan16", "clm_scan16_waves", "clm_collect_ge", "clm_index_count_above", "clm_index_rank",
     "clm_index_lse", "clm_index_lse64", "clm_index_remove", "clm_index_update",
     "clm_text_plan", "clm_gemm_attn",
+    "clm_layernorm_ex", "clm_gemm_ex", "clm_patchify", "clm_write_cls", "clm_gather_pooled", "clm_pool_project",
 )
 CLM_EPI_STORE, CLM_EPI_GELU, CLM_EPI_RESID, CLM_EPI_SCORE = 0, 1, 2, 4
+CLM_EPI_PATCH = 3   # clm_gemm_ex only
 CLM_PROF_GEMM, CLM_PROF_ATTN, CLM_PROF_LN, CLM_PROF_OTHER = 0, 1, 2, 3
 
 

@@ -950,6 +950,125 @@ int clm_gemm_attn(int hip_device, int dtype, int flags, const void* X, int64_t l
   return CLM_OK;
 }
 
+// test hook: every field of LnArgs (layernorm, k_ops.hip) -- the text-embedding gather (mode 1), the
+// dual LayerNorm (g2 / b2, hf), packed rows (m_dev, rowmap)
+int clm_layernorm_ex(int hip_device, int dtype, int mode, const float* src, int64_t lds, const int32_t* ids,
+                     const float* tok, const float* pos, int L, float* hf, int64_t ldh, const float* g1,
+                     const float* b1, const float* g2, const float* b2, float eps, void* y, int64_t ldy, int64_t M,
+                     int d, const int* m_dev, const int* rowmap, void* stream) {
+  if (dtype != CLM_BF16 && dtype != CLM_F16) return fail(CLM_E_ARG, "dtype must be bf16 or f16");
+  if (mode != 0 && mode != 1) return fail(CLM_E_ARG, "layernorm_ex: mode must be 0 (rows) or 1 (token + position gather)");
+  if (M < 0 || M > 0x7FFFFFFF || d <= 0 || d % 128 || d > 1024 || ldy < d || (ldy % 4))
+    return fail(CLM_E_ARG, "bad shape");
+  if (mode == 0 && (lds < d || (lds % 4))) return fail(CLM_E_ARG, "bad shape (lds)");
+  if (hf && (ldh < d || (ldh % 4))) return fail(CLM_E_ARG, "bad shape (ldh)");
+  if (mode == 1 && (!ids || !tok || !pos || !hf)) return fail(CLM_E_ARG, "layernorm_ex: mode 1 needs ids, tok, pos and hf");
+  if (mode == 1 && L < 1) return fail(CLM_E_ARG, "layernorm_ex: mode 1 needs L >= 1");
+  if ((g2 != nullptr) != (b2 != nullptr)) return fail(CLM_E_ARG, "layernorm_ex: g2 and b2 go together");
+  if (g2 && !hf) return fail(CLM_E_ARG, "layernorm_ex: the dual LayerNorm writes hf");
+  if (rowmap && mode != 1) return fail(CLM_E_ARG, "layernorm_ex: rowmap is mode 1's");
+  if (M == 0) return CLM_OK;
+  if ((mode == 0 && !src) || !g1 || !b1 || !y) return fail(CLM_E_ARG, "layernorm_ex: null pointer");
+  DeviceGuard g(hip_device);
+  LnArgs a{};
+  a.mode = mode; a.src = src; a.lds = lds; a.ids = ids; a.tok = tok; a.pos = pos; a.L = L; a.hf = hf; a.ldh = ldh;
+  a.g1 = g1; a.b1 = b1; a.g2 = g2; a.b2 = b2; a.y = (u16*)y; a.ldy = ldy; a.M = (int)M; a.d = d; a.eps = eps;
+  a.m_dev = m_dev; a.rowmap = rowmap;
+  hipError_t e = layernorm(dtype == CLM_BF16, a, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(CLM_E_HIP, std::string("layernorm: ") + hipGetErrorString(e));
+  return CLM_OK;
+}
+
+// test hook: the GEMM forms only the towers run -- EPI_PATCH (aux / aux_ld / group), a device-resident
+// row count (m_dev), and with slices >= 1 the few-row split-K residual GEMM (gemm_splitk_resid)
+int clm_gemm_ex(int hip_device, int dtype, int epilogue, int config, const void* A, int64_t lda, const void* W,
+                int64_t ldw, int M, int N, int K, void* out, int64_t ldo, const float* bias, const float* aux,
+                int64_t aux_ld, int group, const int* m_dev, int slices, float* ws, void* stream) {
+  if (dtype != CLM_BF16 && dtype != CLM_F16) return fail(CLM_E_ARG, "dtype must be bf16 or f16");
+  if (epilogue != EPI_STORE && epilogue != EPI_GELU && epilogue != EPI_RESID && epilogue != EPI_PATCH)
+    return fail(CLM_E_ARG, "gemm_ex: epilogue must be STORE, GELU, RESID or PATCH");
+  if (config >= gemm_num_configs()) return fail(CLM_E_ARG, "bad config");
+  const int64_t kr = ((int64_t)K + 63) / 64 * 64;
+  if (M < 0 || N < 0 || K <= 0 || K % 32 || (K % 64 && (lda < kr || ldw < kr)) || lda < K || ldw < K || ldo < N)
+    return fail(CLM_E_ARG, "bad shape (K % 64 == 0, or K % 64 == 32 with lda, ldw >= round_up(K, 64); ldo >= N)");
+  if (epilogue == EPI_PATCH) {
+    if (!aux || aux_ld < N || group < 1 || M % group)
+      return fail(CLM_E_ARG, "gemm_ex: EPI_PATCH needs aux, aux_ld >= N, group >= 1 and M % group == 0");
+  } else if (aux || aux_ld || group) {
+    return fail(CLM_E_ARG, "gemm_ex: aux, aux_ld and group are EPI_PATCH's");
+  }
+  if (slices < 0 || (slices == 0 && ws)) return fail(CLM_E_ARG, "gemm_ex: ws goes with slices >= 1");
+  if (slices > 0 && (epilogue != EPI_RESID || m_dev || (config >= 0 && config != GEMM_CFG_SPLITK)))
+    return fail(CLM_E_ARG, "gemm_ex: split-K is EPI_RESID on the 128 x 64 tile, without m_dev");
+  if (M == 0 || N == 0) return CLM_OK;
+  if (!A || !W || !out) return fail(CLM_E_ARG, "gemm_ex: null pointer");
+  DeviceGuard g(hip_device);
+  GemmArgs a{};
+  a.A = (const u16*)A; a.lda = lda; a.W = (const u16*)W; a.ldw = ldw; a.M = M; a.N = N; a.K = K;
+  a.out = out; a.ldo = ldo; a.bias = bias; a.aux = aux; a.aux_ld = aux_ld; a.group = group; a.m_dev = m_dev;
+  const bool bf = dtype == CLM_BF16;
+  const hipError_t e = slices > 0 ? gemm_splitk_resid(bf, a, slices, ws, (hipStream_t)stream)
+                                  : gemm_cfg(bf, epilogue, config, a, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(CLM_E_HIP, std::string("gemm: ") + hipGetErrorString(e));
+  return CLM_OK;
+}
+
+// test hooks: the image prologue's and the pooled tail's row ops (k_ops.hip), as the launchers take them
+int clm_patchify(int hip_device, int dtype, const void* pix, int layout, int B, int S, int p, int C,
+                 const float* lut, void* P, int Kp, void* stream) {
+  if (dtype != CLM_BF16 && dtype != CLM_F16) return fail(CLM_E_ARG, "dtype must be bf16 or f16");
+  if (layout != CLM_PIX_U8_HWC && layout != CLM_PIX_F32_CHW) return fail(CLM_E_ARG, "bad pixel layout");
+  if (B < 0 || S < 1 || p < 1 || S % p || C < 1 || C > 4 || S > 4096)
+    return fail(CLM_E_ARG, "patchify: B >= 0, 1 <= p, S % p == 0, S <= 4096, 1 <= C <= 4");
+  if (Kp < C * p * p) return fail(CLM_E_ARG, "patchify: Kp < C * p * p");
+  if (B == 0) return CLM_OK;
+  if (!pix || !lut || !P) return fail(CLM_E_ARG, "patchify: null pointer");
+  DeviceGuard g(hip_device);
+  hipError_t e = patchify(dtype == CLM_BF16, pix, layout == CLM_PIX_U8_HWC ? 0 : 1, B, S, p, C, lut, (u16*)P, Kp,
+                          (hipStream_t)stream);
+  if (e != hipSuccess) return fail(CLM_E_HIP, std::string("patchify: ") + hipGetErrorString(e));
+  return CLM_OK;
+}
+
+int clm_write_cls(int hip_device, float* h, int64_t ldh, int B, int T, int d, const float* cls, const float* pos,
+                  void* stream) {
+  if (B < 0 || T < 1 || d < 1 || ldh < d) return fail(CLM_E_ARG, "write_cls: B >= 0, T >= 1, 1 <= d <= ldh");
+  if (B == 0) return CLM_OK;
+  if (!h || !cls || !pos) return fail(CLM_E_ARG, "write_cls: null pointer");
+  DeviceGuard g(hip_device);
+  hipError_t e = write_cls(h, ldh, B, T, d, cls, pos, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(CLM_E_HIP, std::string("write_cls: ") + hipGetErrorString(e));
+  return CLM_OK;
+}
+
+int clm_gather_pooled(int hip_device, const float* h, int64_t ldh, const void* O, int64_t ldo, int B, int T, int d,
+                      const int32_t* ids, int eos, float* hc, void* Oc, int64_t ldoc, const int* offs, void* stream) {
+  if (B < 0 || T < 1 || d < 1 || ldh < d || ldo < d || ldoc < d)
+    return fail(CLM_E_ARG, "gather_pooled: B >= 0, T >= 1, 1 <= d <= ldh, ldo, ldoc");
+  if (B == 0) return CLM_OK;
+  if (!h || !O || !hc || !Oc) return fail(CLM_E_ARG, "gather_pooled: null pointer");
+  DeviceGuard g(hip_device);
+  hipError_t e = gather_pooled(h, ldh, (const u16*)O, ldo, B, T, d, ids, eos, hc, (u16*)Oc, ldoc, (hipStream_t)stream,
+                               offs);
+  if (e != hipSuccess) return fail(CLM_E_HIP, std::string("gather_pooled: ") + hipGetErrorString(e));
+  return CLM_OK;
+}
+
+int clm_pool_project(int hip_device, const float* h, int64_t ldh, int B, int T, int d, const int32_t* ids, int eos,
+                     const float* gamma, const float* beta, float eps, const float* projT, int D, float* tmp,
+                     void* out, int out_dtype, int normalize, const int* offs, void* stream) {
+  if (out_dtype != CLM_F32 && out_dtype != CLM_F16) return fail(CLM_E_ARG, "out_dtype must be f32 or f16");
+  if (B < 0 || T < 1 || d < 1 || d > 1024 || D < 1 || ldh < d)
+    return fail(CLM_E_ARG, "pool_project: B >= 0, T >= 1, 1 <= d <= min(ldh, 1024), D >= 1");
+  if (B == 0) return CLM_OK;
+  if (!h || !gamma || !beta || !projT || !tmp || !out) return fail(CLM_E_ARG, "pool_project: null pointer");
+  DeviceGuard g(hip_device);
+  hipError_t e = pool_project(h, ldh, B, T, d, ids, eos, gamma, beta, eps, projT, D, tmp, out,
+                              out_dtype == CLM_F32 ? 0 : 1, normalize, (hipStream_t)stream, offs);
+  if (e != hipSuccess) return fail(CLM_E_HIP, std::string("pool_project: ") + hipGetErrorString(e));
+  return CLM_OK;
+}
+
 int clm_prof_enable(clm_ctx* ctx, int enable) {
   if (!ctx) return fail(CLM_E_ARG, "null ctx");
   DeviceGuard g(ctx->dev);

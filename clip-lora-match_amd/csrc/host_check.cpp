@@ -113,6 +113,159 @@ static void argument_checks() {
     CHECK(clm_gemm_attn(0, CLM_F16, 0, nullptr, 64, nullptr, 64, nullptr, nullptr, 64, 0, 1, 1, 64, nullptr, nullptr,
                         nullptr, nullptr, nullptr) == CLM_OK);   // B = 0: nothing to do
   }
+  {   // the encoder row-op and tower-GEMM hooks: every case is refused (or empty) before any launch
+    float f[4] = {0.f, 0.f, 0.f, 0.f};
+    uint16_t x[1] = {0};
+    const int32_t id1[1] = {0};
+    int one[2] = {0, 0};
+    // clm_layernorm_ex(dev, dtype, mode, src, lds, ids, tok, pos, L, hf, ldh, g1, b1, g2, b2, eps, y, ldy, M, d,
+    //                  m_dev, rowmap, stream)
+    CHECK(clm_layernorm_ex(0, CLM_F32, 0, f, 128, nullptr, nullptr, nullptr, 0, nullptr, 0, f, f, nullptr, nullptr,
+                           1e-5f, x, 128, 1, 128, nullptr, nullptr, nullptr) == CLM_E_ARG);   // dtype
+    CHECK(clm_layernorm_ex(0, CLM_F16, 2, f, 128, nullptr, nullptr, nullptr, 0, nullptr, 0, f, f, nullptr, nullptr,
+                           1e-5f, x, 128, 1, 128, nullptr, nullptr, nullptr) == CLM_E_ARG);   // mode
+    CHECK(clm_layernorm_ex(0, CLM_F16, 0, f, 128, nullptr, nullptr, nullptr, 0, nullptr, 0, f, f, nullptr, nullptr,
+                           1e-5f, x, 128, -1, 128, nullptr, nullptr, nullptr) == CLM_E_ARG);  // M < 0
+    CHECK(clm_layernorm_ex(0, CLM_F16, 0, f, 100, nullptr, nullptr, nullptr, 0, nullptr, 0, f, f, nullptr, nullptr,
+                           1e-5f, x, 100, 1, 100, nullptr, nullptr, nullptr) == CLM_E_ARG);   // d % 128
+    CHECK(clm_layernorm_ex(0, CLM_F16, 0, f, 128, nullptr, nullptr, nullptr, 0, nullptr, 0, f, f, nullptr, nullptr,
+                           1e-5f, x, 130, 1, 128, nullptr, nullptr, nullptr) == CLM_E_ARG);   // ldy % 4
+    CHECK(clm_layernorm_ex(0, CLM_F16, 0, nullptr, 128, nullptr, nullptr, nullptr, 0, nullptr, 0, f, f, nullptr,
+                           nullptr, 1e-5f, x, 128, 1, 128, nullptr, nullptr, nullptr) == CLM_E_ARG);   // null src
+    CHECK(clm_layernorm_ex(0, CLM_F16, 0, f, 128, nullptr, nullptr, nullptr, 0, nullptr, 0, f, nullptr, nullptr,
+                           nullptr, 1e-5f, x, 128, 1, 128, nullptr, nullptr, nullptr) == CLM_E_ARG);   // null beta
+    CHECK(clm_layernorm_ex(0, CLM_F16, 1, nullptr, 0, nullptr, f, f, 1, f, 128, f, f, nullptr, nullptr, 1e-5f, x,
+                           128, 1, 128, nullptr, nullptr, nullptr) == CLM_E_ARG);   // mode 1 without ids
+    CHECK(clm_layernorm_ex(0, CLM_F16, 1, nullptr, 0, id1, nullptr, f, 1, f, 128, f, f, nullptr, nullptr, 1e-5f, x,
+                           128, 1, 128, nullptr, nullptr, nullptr) == CLM_E_ARG);   // ... tok
+    CHECK(clm_layernorm_ex(0, CLM_F16, 1, nullptr, 0, id1, f, nullptr, 1, f, 128, f, f, nullptr, nullptr, 1e-5f, x,
+                           128, 1, 128, nullptr, nullptr, nullptr) == CLM_E_ARG);   // ... pos
+    CHECK(clm_layernorm_ex(0, CLM_F16, 1, nullptr, 0, id1, f, f, 1, nullptr, 0, f, f, nullptr, nullptr, 1e-5f, x,
+                           128, 1, 128, nullptr, nullptr, nullptr) == CLM_E_ARG);   // ... hf
+    CHECK(clm_layernorm_ex(0, CLM_F16, 1, nullptr, 0, id1, f, f, 0, f, 128, f, f, nullptr, nullptr, 1e-5f, x, 128, 1,
+                           128, nullptr, nullptr, nullptr) == CLM_E_ARG);   // L < 1
+    CHECK(clm_layernorm_ex(0, CLM_F16, 1, nullptr, 0, id1, f, f, 1, f, 64, f, f, nullptr, nullptr, 1e-5f, x, 128, 1,
+                           128, nullptr, nullptr, nullptr) == CLM_E_ARG);   // ldh < d
+    CHECK(clm_layernorm_ex(0, CLM_F16, 0, f, 128, nullptr, nullptr, nullptr, 0, f, 128, f, f, f, nullptr, 1e-5f, x,
+                           128, 1, 128, nullptr, nullptr, nullptr) == CLM_E_ARG);   // g2 without b2
+    CHECK(clm_layernorm_ex(0, CLM_F16, 0, f, 128, nullptr, nullptr, nullptr, 0, nullptr, 0, f, f, f, f, 1e-5f, x, 128,
+                           1, 128, nullptr, nullptr, nullptr) == CLM_E_ARG);   // the dual LN without hf
+    CHECK(clm_layernorm_ex(0, CLM_F16, 0, f, 128, nullptr, nullptr, nullptr, 0, nullptr, 0, f, f, nullptr, nullptr,
+                           1e-5f, x, 128, 1, 128, nullptr, one, nullptr) == CLM_E_ARG);   // rowmap in mode 0
+    CHECK(clm_layernorm_ex(0, CLM_F16, 0, nullptr, 128, nullptr, nullptr, nullptr, 0, nullptr, 0, nullptr, nullptr,
+                           nullptr, nullptr, 1e-5f, nullptr, 128, 0, 128, nullptr, nullptr, nullptr) == CLM_OK);   // M = 0
+    // clm_gemm_ex(dev, dtype, epi, config, A, lda, W, ldw, M, N, K, out, ldo, bias, aux, aux_ld, group, m_dev,
+    //             slices, ws, stream)
+    CHECK(clm_gemm_ex(0, 99, CLM_EPI_STORE, -1, x, 64, x, 64, 1, 1, 64, x, 1, nullptr, nullptr, 0, 0, nullptr, 0,
+                      nullptr, nullptr) == CLM_E_ARG);   // dtype
+    CHECK(clm_gemm_ex(0, CLM_F16, CLM_EPI_SCORE, -1, x, 64, x, 64, 1, 1, 64, x, 1, nullptr, nullptr, 0, 0, nullptr, 0,
+                      nullptr, nullptr) == CLM_E_ARG);   // not an encoder epilogue
+    CHECK(clm_gemm_ex(0, CLM_F16, CLM_EPI_STORE, 99, x, 64, x, 64, 1, 1, 64, x, 1, nullptr, nullptr, 0, 0, nullptr, 0,
+                      nullptr, nullptr) == CLM_E_ARG);   // config
+    CHECK(clm_gemm_ex(0, CLM_F16, CLM_EPI_STORE, -1, x, 64, x, 64, -1, 1, 64, x, 1, nullptr, nullptr, 0, 0, nullptr, 0,
+                      nullptr, nullptr) == CLM_E_ARG);   // M < 0
+    CHECK(clm_gemm_ex(0, CLM_F16, CLM_EPI_STORE, -1, x, 64, x, 64, 1, 1, 48, x, 1, nullptr, nullptr, 0, 0, nullptr, 0,
+                      nullptr, nullptr) == CLM_E_ARG);   // K % 32
+    CHECK(clm_gemm_ex(0, CLM_F16, CLM_EPI_STORE, -1, x, 96, x, 128, 1, 1, 96, x, 1, nullptr, nullptr, 0, 0, nullptr, 0,
+                      nullptr, nullptr) == CLM_E_ARG);   // K % 64 == 32 with lda < round_up(K, 64)
+    CHECK(clm_gemm_ex(0, CLM_F16, CLM_EPI_STORE, -1, x, 64, x, 64, 1, 8, 64, x, 4, nullptr, nullptr, 0, 0, nullptr, 0,
+                      nullptr, nullptr) == CLM_E_ARG);   // ldo < N
+    CHECK(clm_gemm_ex(0, CLM_F16, CLM_EPI_STORE, -1, nullptr, 64, x, 64, 1, 1, 64, x, 1, nullptr, nullptr, 0, 0,
+                      nullptr, 0, nullptr, nullptr) == CLM_E_ARG);   // null A
+    CHECK(clm_gemm_ex(0, CLM_F16, CLM_EPI_STORE, -1, x, 64, x, 64, 1, 1, 64, nullptr, 1, nullptr, nullptr, 0, 0,
+                      nullptr, 0, nullptr, nullptr) == CLM_E_ARG);   // null out
+    CHECK(clm_gemm_ex(0, CLM_F16, CLM_EPI_PATCH, -1, x, 64, x, 64, 4, 4, 64, f, 4, nullptr, nullptr, 4, 2, nullptr, 0,
+                      nullptr, nullptr) == CLM_E_ARG);   // PATCH without aux
+    CHECK(clm_gemm_ex(0, CLM_F16, CLM_EPI_PATCH, -1, x, 64, x, 64, 4, 4, 64, f, 4, nullptr, f, 4, 0, nullptr, 0,
+                      nullptr, nullptr) == CLM_E_ARG);   // group < 1
+    CHECK(clm_gemm_ex(0, CLM_F16, CLM_EPI_PATCH, -1, x, 64, x, 64, 4, 4, 64, f, 4, nullptr, f, 4, 3, nullptr, 0,
+                      nullptr, nullptr) == CLM_E_ARG);   // M % group
+    CHECK(clm_gemm_ex(0, CLM_F16, CLM_EPI_PATCH, -1, x, 64, x, 64, 4, 4, 64, f, 4, nullptr, f, 2, 2, nullptr, 0,
+                      nullptr, nullptr) == CLM_E_ARG);   // aux_ld < N
+    CHECK(clm_gemm_ex(0, CLM_F16, CLM_EPI_PATCH, -1, x, 64, x, 64, 4, 4, 64, f, 4, f, f, 4, 2, nullptr, 0, nullptr,
+                      nullptr) == CLM_E_HIP);   // PATCH with a bias: the launcher's rule, before any launch
+    CHECK(clm_gemm_ex(0, CLM_F16, CLM_EPI_RESID, -1, x, 64, x, 64, 4, 4, 64, f, 4, nullptr, f, 4, 2, nullptr, 0,
+                      nullptr, nullptr) == CLM_E_ARG);   // aux / group with another epilogue
+    CHECK(clm_gemm_ex(0, CLM_F16, CLM_EPI_RESID, -1, x, 64, x, 64, 4, 4, 64, f, 4, nullptr, nullptr, 0, 0, nullptr, -1,
+                      nullptr, nullptr) == CLM_E_ARG);   // slices < 0
+    CHECK(clm_gemm_ex(0, CLM_F16, CLM_EPI_RESID, -1, x, 64, x, 64, 4, 4, 64, f, 4, nullptr, nullptr, 0, 0, nullptr, 0,
+                      f, nullptr) == CLM_E_ARG);   // a workspace without slices
+    CHECK(clm_gemm_ex(0, CLM_F16, CLM_EPI_STORE, -1, x, 64, x, 64, 4, 4, 64, x, 4, nullptr, nullptr, 0, 0, nullptr, 1,
+                      f, nullptr) == CLM_E_ARG);   // split-K is RESID's
+    CHECK(clm_gemm_ex(0, CLM_F16, CLM_EPI_RESID, 0, x, 64, x, 64, 4, 4, 64, f, 4, nullptr, nullptr, 0, 0, nullptr, 1, f,
+                      nullptr) == CLM_E_ARG);   // ... on config 2 only
+    CHECK(clm_gemm_ex(0, CLM_F16, CLM_EPI_RESID, -1, x, 64, x, 64, 4, 4, 64, f, 4, nullptr, nullptr, 0, 0, one, 1, f,
+                      nullptr) == CLM_E_ARG);   // ... without m_dev
+    CHECK(clm_gemm_ex(0, CLM_F16, CLM_EPI_RESID, -1, x, 64, x, 64, 4, 4, 64, f, 4, nullptr, nullptr, 0, 0, nullptr, 1,
+                      nullptr, nullptr) == CLM_E_HIP);   // no workspace: the launcher's
+    CHECK(clm_gemm_ex(0, CLM_F16, CLM_EPI_RESID, -1, x, 128, x, 128, 4, 4, 128, f, 4, nullptr, nullptr, 0, 0, nullptr,
+                      3, f, nullptr) == CLM_E_HIP);   // K % (64 slices)
+    CHECK(clm_gemm_ex(0, CLM_F16, CLM_EPI_RESID, -1, x, 64, x, 64, 4, 6, 64, f, 6, nullptr, nullptr, 0, 0, nullptr, 1, f,
+                      nullptr) == CLM_E_HIP);   // N % 4
+    CHECK(clm_gemm_ex(0, CLM_F16, CLM_EPI_STORE, -1, nullptr, 64, nullptr, 64, 0, 4, 64, nullptr, 4, nullptr, nullptr,
+                      0, 0, nullptr, 0, nullptr, nullptr) == CLM_OK);   // M = 0
+    // clm_patchify(dev, dtype, pix, layout, B, S, p, C, lut, P, Kp, stream)
+    CHECK(clm_patchify(0, CLM_F32, x, CLM_PIX_U8_HWC, 1, 16, 8, 3, f, x, 192, nullptr) == CLM_E_ARG);   // dtype
+    CHECK(clm_patchify(0, CLM_F16, x, 7, 1, 16, 8, 3, f, x, 192, nullptr) == CLM_E_ARG);                // layout
+    CHECK(clm_patchify(0, CLM_F16, x, CLM_PIX_U8_HWC, -1, 16, 8, 3, f, x, 192, nullptr) == CLM_E_ARG);
+    CHECK(clm_patchify(0, CLM_F16, x, CLM_PIX_U8_HWC, 1, 16, 0, 3, f, x, 192, nullptr) == CLM_E_ARG);   // p < 1
+    CHECK(clm_patchify(0, CLM_F16, x, CLM_PIX_U8_HWC, 1, 16, 5, 3, f, x, 192, nullptr) == CLM_E_ARG);   // S % p
+    CHECK(clm_patchify(0, CLM_F16, x, CLM_PIX_U8_HWC, 1, 16, 8, 0, f, x, 192, nullptr) == CLM_E_ARG);   // C < 1
+    CHECK(clm_patchify(0, CLM_F16, x, CLM_PIX_U8_HWC, 1, 16, 8, 3, f, x, 128, nullptr) == CLM_E_ARG);   // Kp < C p^2
+    CHECK(clm_patchify(0, CLM_F16, nullptr, CLM_PIX_U8_HWC, 1, 16, 8, 3, f, x, 192, nullptr) == CLM_E_ARG);
+    CHECK(clm_patchify(0, CLM_F16, x, CLM_PIX_F32_CHW, 1, 16, 8, 3, nullptr, x, 192, nullptr) == CLM_E_ARG);   // no lut
+    CHECK(clm_patchify(0, CLM_F16, x, CLM_PIX_U8_HWC, 1, 16, 8, 3, f, nullptr, 192, nullptr) == CLM_E_ARG);
+    CHECK(clm_patchify(0, CLM_F16, x, CLM_PIX_U8_HWC, 1, 16, 8, 3, f, x, 196, nullptr) == CLM_E_HIP);   // Kp % 8
+    CHECK(clm_patchify(0, CLM_F16, nullptr, CLM_PIX_U8_HWC, 0, 16, 8, 3, nullptr, nullptr, 192, nullptr) == CLM_OK);
+    // clm_write_cls(dev, h, ldh, B, T, d, cls, pos, stream)
+    CHECK(clm_write_cls(0, f, 4, -1, 1, 4, f, f, nullptr) == CLM_E_ARG);
+    CHECK(clm_write_cls(0, f, 4, 1, 0, 4, f, f, nullptr) == CLM_E_ARG);
+    CHECK(clm_write_cls(0, f, 2, 1, 1, 4, f, f, nullptr) == CLM_E_ARG);   // ldh < d
+    CHECK(clm_write_cls(0, nullptr, 4, 1, 1, 4, f, f, nullptr) == CLM_E_ARG);
+    CHECK(clm_write_cls(0, f, 4, 1, 1, 4, nullptr, f, nullptr) == CLM_E_ARG);
+    CHECK(clm_write_cls(0, f, 4, 1, 1, 4, f, nullptr, nullptr) == CLM_E_ARG);
+    CHECK(clm_write_cls(0, nullptr, 4, 0, 1, 4, nullptr, nullptr, nullptr) == CLM_OK);
+    // clm_gather_pooled(dev, h, ldh, O, ldo, B, T, d, ids, eos, hc, Oc, ldoc, offs, stream)
+    CHECK(clm_gather_pooled(0, f, 4, x, 4, -1, 1, 4, nullptr, 2, f, x, 4, nullptr, nullptr) == CLM_E_ARG);
+    CHECK(clm_gather_pooled(0, f, 4, x, 4, 1, 0, 4, nullptr, 2, f, x, 4, nullptr, nullptr) == CLM_E_ARG);   // T < 1
+    CHECK(clm_gather_pooled(0, f, 4, x, 4, 1, 1, 8, nullptr, 2, f, x, 8, nullptr, nullptr) == CLM_E_ARG);   // ldh < d
+    CHECK(clm_gather_pooled(0, f, 4, x, 4, 1, 1, 4, nullptr, 2, f, x, 2, nullptr, nullptr) == CLM_E_ARG);   // ldoc < d
+    CHECK(clm_gather_pooled(0, nullptr, 4, x, 4, 1, 1, 4, nullptr, 2, f, x, 4, nullptr, nullptr) == CLM_E_ARG);
+    CHECK(clm_gather_pooled(0, f, 4, nullptr, 4, 1, 1, 4, nullptr, 2, f, x, 4, nullptr, nullptr) == CLM_E_ARG);
+    CHECK(clm_gather_pooled(0, f, 4, x, 4, 1, 1, 4, nullptr, 2, nullptr, x, 4, nullptr, nullptr) == CLM_E_ARG);
+    CHECK(clm_gather_pooled(0, f, 4, x, 4, 1, 1, 4, nullptr, 2, f, nullptr, 4, nullptr, nullptr) == CLM_E_ARG);
+    CHECK(clm_gather_pooled(0, f, 6, x, 8, 1, 1, 4, nullptr, 2, f, x, 4, nullptr, nullptr) == CLM_E_HIP);   // ldh % 4
+    CHECK(clm_gather_pooled(0, nullptr, 4, nullptr, 4, 0, 1, 4, nullptr, 2, nullptr, nullptr, 4, nullptr, nullptr) ==
+          CLM_OK);
+    // clm_pool_project(dev, h, ldh, B, T, d, ids, eos, gamma, beta, eps, projT, D, tmp, out, out_dtype, normalize,
+    //                  offs, stream)
+    CHECK(clm_pool_project(0, f, 16, 1, 1, 16, nullptr, 2, f, f, 1e-5f, f, 4, f, f, CLM_BF16, 1, nullptr, nullptr) ==
+          CLM_E_ARG);   // out dtype
+    CHECK(clm_pool_project(0, f, 16, -1, 1, 16, nullptr, 2, f, f, 1e-5f, f, 4, f, f, CLM_F32, 1, nullptr, nullptr) ==
+          CLM_E_ARG);
+    CHECK(clm_pool_project(0, f, 16, 1, 0, 16, nullptr, 2, f, f, 1e-5f, f, 4, f, f, CLM_F32, 1, nullptr, nullptr) ==
+          CLM_E_ARG);   // T < 1
+    CHECK(clm_pool_project(0, f, 8, 1, 1, 16, nullptr, 2, f, f, 1e-5f, f, 4, f, f, CLM_F32, 1, nullptr, nullptr) ==
+          CLM_E_ARG);   // ldh < d
+    CHECK(clm_pool_project(0, f, 2048, 1, 1, 2048, nullptr, 2, f, f, 1e-5f, f, 4, f, f, CLM_F32, 1, nullptr, nullptr) ==
+          CLM_E_ARG);   // d > 1024
+    CHECK(clm_pool_project(0, f, 16, 1, 1, 16, nullptr, 2, f, f, 1e-5f, f, 0, f, f, CLM_F32, 1, nullptr, nullptr) ==
+          CLM_E_ARG);   // D < 1
+    CHECK(clm_pool_project(0, nullptr, 16, 1, 1, 16, nullptr, 2, f, f, 1e-5f, f, 4, f, f, CLM_F32, 1, nullptr,
+                           nullptr) == CLM_E_ARG);
+    CHECK(clm_pool_project(0, f, 16, 1, 1, 16, nullptr, 2, nullptr, f, 1e-5f, f, 4, f, f, CLM_F32, 1, nullptr,
+                           nullptr) == CLM_E_ARG);
+    CHECK(clm_pool_project(0, f, 16, 1, 1, 16, nullptr, 2, f, f, 1e-5f, nullptr, 4, f, f, CLM_F32, 1, nullptr,
+                           nullptr) == CLM_E_ARG);
+    CHECK(clm_pool_project(0, f, 16, 1, 1, 16, nullptr, 2, f, f, 1e-5f, f, 4, nullptr, f, CLM_F32, 1, nullptr,
+                           nullptr) == CLM_E_ARG);
+    CHECK(clm_pool_project(0, f, 16, 1, 1, 16, nullptr, 2, f, f, 1e-5f, f, 4, f, nullptr, CLM_F32, 1, nullptr,
+                           nullptr) == CLM_E_ARG);
+    CHECK(clm_pool_project(0, f, 24, 1, 1, 24, nullptr, 2, f, f, 1e-5f, f, 4, f, f, CLM_F32, 1, nullptr, nullptr) ==
+          CLM_E_HIP);   // d % 16
+    CHECK(clm_pool_project(0, nullptr, 16, 0, 1, 16, nullptr, 2, nullptr, nullptr, 1e-5f, nullptr, 4, nullptr, nullptr,
+                           CLM_F32, 1, nullptr, nullptr) == CLM_OK);
+  }
   CHECK(clm_topk_merge(0, nullptr, nullptr, 1, 0, 1, 1, nullptr, nullptr, nullptr) != CLM_OK);
   CHECK(clm_l2_normalize(0, nullptr, 1, 0, nullptr) != CLM_OK);
   CHECK(clm_scan16(0, nullptr, nullptr, -1, 64, nullptr, nullptr, 1, nullptr, 1, nullptr, nullptr, 0, nullptr) ==

@@ -384,6 +384,9 @@ int gemm_num_configs() { return NCFG; }
 hipError_t gemm_cfg(bool bf16, int epi, int config, const GemmArgs& g, hipStream_t s) {
   if (g.M <= 0 || g.N <= 0) return hipSuccess;
   if (g.K <= 0 || (g.K % 32) != 0 || (g.lda % 8) != 0 || (g.ldw % 8) != 0) return hipErrorInvalidValue;
+  // EPI_PATCH takes no bias (the patch convolution has none; aux carries the position rows): the
+  // vector epilogue would add one, the ragged-N scalar epilogue would not
+  if (epi == EPI_PATCH && (g.bias || !g.aux || g.group < 1)) return hipErrorInvalidValue;
   int id = config >= 0 ? config : pick_config(epi, g.M, g.N);
   if (g.K % BK) {   // the half last K-step: gemm_kernel configs without split-K only
     if (g.ksplit > 1) return hipErrorInvalidValue;

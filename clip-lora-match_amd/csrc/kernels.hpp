@@ -13,7 +13,8 @@ enum Epi {
   EPI_STORE = 0,  // out16[m,n] = acc + bias[n]
   EPI_GELU = 1,   // out16[m,n] = quick_gelu(acc + bias[n])
   EPI_RESID = 2,  // outf[m,n] += acc + bias[n]            (fp32 residual stream)
-  EPI_PATCH = 3,  // outf[b*(G+1)+1+p, n] = acc + aux[(1+p)*aux_ld + n], m = b*G+p
+  EPI_PATCH = 3,  // outf[b*(G+1)+1+p, n] = acc + aux[(1+p)*aux_ld + n], m = b*G+p, G = group >= 1;
+                  // no bias: gemm_cfg refuses one (hipErrorInvalidValue), as it does a null aux
   EPI_SCORE = 4,  // outf[m,n] = acc * rscale[m] * cscale[n]  (cosine scores)
   EPI_FILTER = 5,  // s = acc*rscale[m]*cscale[n]; if s >= theta[m]: append (s, base+n) to row m's
                    // candidate list (atomic slot in cnt[m], capacity cap)

@@ -406,6 +406,63 @@ int clm_text_plan(int hip_device, const int32_t* ids, int B, int L, int eos, int
 int clm_gemm_attn(int hip_device, int dtype, int flags, const void* X, int64_t ldx, const void* W, int64_t ldw,
                   const float* bias, void* out, int64_t ldo, int B, int T, int H, int K, const int* lens,
                   const int* offs, const int* tiles, const int* counts, void* stream);
+/* Test hooks over the encoder's remaining launchers (device pointers; every extent is the caller's to
+ * provide). Each checks its arguments (CLM_E_ARG) before anything is launched; what the launcher
+ * itself refuses is CLM_E_HIP, with nothing written.
+ *
+ * clm_layernorm_ex: the LayerNorm kernel with every option (d, ldy, dtype as clm_layernorm).
+ *   mode 0: x = src [M, lds] rows. mode 1 (text embeddings): x = tok[ids[s]] + pos[s % L], one fp32 add,
+ *   s = r, or rowmap[r] where rowmap (clm_text_plan's; mode 1 only) is given; tok [vocab, d], pos [L, d],
+ *   ids indexed by s; x is written to hf [M, ldh].
+ *   g2 / b2 NULL: y = LN(x; g1, b1). Both set (the dual LayerNorm): hf = LN(x; g1, b1) in fp32 (hf may be
+ *   src: in place) and y = LN(hf; g2, b2). hf is required by mode 1 and by g2, otherwise unused.
+ *   m_dev (or NULL): only rows r < *m_dev (a device int, <= M) are computed; M sizes the grid, rows at
+ *   or past *m_dev are untouched and *m_dev == 0 writes nothing.
+ *   CLM_E_ARG: what clm_layernorm refuses; mode not 0 / 1; mode 1 with a null ids, tok, pos or hf or
+ *   L < 1; ldh < d or ldh % 4 with hf; one of g2 / b2 alone; g2 without hf; rowmap in mode 0. M == 0 is
+ *   CLM_OK. */
+int clm_layernorm_ex(int hip_device, int dtype, int mode, const float* src, int64_t lds, const int32_t* ids,
+                     const float* tok, const float* pos, int L, float* hf, int64_t ldh, const float* g1,
+                     const float* b1, const float* g2, const float* b2, float eps, void* y, int64_t ldy, int64_t M,
+                     int d, const int* m_dev, const int* rowmap, void* stream);
+/* clm_gemm_ex: clm_gemm's STORE / GELU / RESID (operands and shapes as there, ldo >= N) plus
+ *   CLM_EPI_PATCH: out (fp32) [b (group + 1) + 1 + p, n] = acc + aux[(1 + p) aux_ld + n] for row m =
+ *   b group + p -- the patch embeddings written around each image's class row, which is not touched.
+ *   aux [group + 1, aux_ld >= N] fp32, group >= 1, M % group == 0, and no bias: one given is refused by
+ *   the launcher (CLM_E_HIP); configs 13 / 14 do not have this epilogue (CLM_E_HIP). aux, aux_ld and
+ *   group are NULL / 0 / 0 for the other epilogues.
+ *   m_dev (or NULL): the row count is *m_dev (a device int, <= M, which sizes the grid); rows at or
+ *   past it are untouched, *m_dev == 0 writes nothing.
+ *   slices >= 1 (CLM_EPI_RESID only, config -1 or 2, no m_dev): the few-row split-K form, out += acc +
+ *   bias with K cut into `slices` (a divisor of K / 64) whose fp32 partials go to ws [slices * M * N]
+ *   and are summed in slice order, so a row's bits do not depend on M; N % 4 == 0, ldo % 4 == 0.
+ *   slices == 0: the plain GEMM, ws NULL. */
+enum { CLM_EPI_PATCH = 3 };
+int clm_gemm_ex(int hip_device, int dtype, int epilogue, int config, const void* A, int64_t lda, const void* W,
+                int64_t ldw, int M, int N, int K, void* out, int64_t ldo, const float* bias, const float* aux,
+                int64_t aux_ld, int group, const int* m_dev, int slices, float* ws, void* stream);
+/* clm_patchify: pixels (CLM_PIX_U8_HWC [B, S, S, C] bytes through lut [C, 256], or CLM_PIX_F32_CHW
+ *   [B, C, S, S] copied) -> P [B (S/p)^2, Kp] in dtype CLM_BF16|CLM_F16, row b G^2 + py G + px, column
+ *   c p^2 + ky p + kx, columns [C p^2, Kp) zero. S % p == 0, 1 <= C <= 4, Kp >= C p^2 (CLM_E_ARG), Kp
+ *   % 8 == 0 (the launcher's). lut is required for either layout. */
+int clm_patchify(int hip_device, int dtype, const void* pix, int layout, int B, int S, int p, int C,
+                 const float* lut, void* P, int Kp, void* stream);
+/* clm_write_cls: h[b T, 0:d] = cls[0:d] + pos[0:d] for b < B, h fp32 with row stride ldh >= d */
+int clm_write_cls(int hip_device, float* h, int64_t ldh, int B, int T, int d, const float* cls, const float* pos,
+                  void* stream);
+/* The pooled row of item b: offs[b + 1] - 1 where offs (clm_text_plan's) is given; else b T + t with t =
+ * 0 where ids is NULL, else over ids[b, 0:T] the first t with ids == eos (0 if none), or with eos == 2 the
+ * first largest id.
+ * clm_gather_pooled: hc [B, d] fp32 = h's pooled rows, Oc [B, ldoc] = O's (16-bit values, columns
+ *   0:d); d, ldh, ldo, ldoc multiples of 4 (the launcher's).
+ * clm_pool_project: pooled row -> LayerNorm(gamma, beta, eps) -> . projT [d, D] (fp32) -> tmp [B, D] ->
+ *   divided by its L2 norm if normalize -> out [B, D] in out_dtype CLM_F32|CLM_F16. d <= 1024, d % 16 ==
+ *   0 (the launcher's). A row's bits depend on neither B nor its position in the batch. */
+int clm_gather_pooled(int hip_device, const float* h, int64_t ldh, const void* O, int64_t ldo, int B, int T, int d,
+                      const int32_t* ids, int eos, float* hc, void* Oc, int64_t ldoc, const int* offs, void* stream);
+int clm_pool_project(int hip_device, const float* h, int64_t ldh, int B, int T, int d, const int32_t* ids, int eos,
+                     const float* gamma, const float* beta, float eps, const float* projT, int D, float* tmp,
+                     void* out, int out_dtype, int normalize, const int* offs, void* stream);
 
 /* Kernel timing by category, measured with hipEvents recorded on the launch
  * stream around every kernel of clm_encode_* while enabled (adds event
