@@ -92,6 +92,9 @@ def lib():
                                   c_void_p]),
         "clm_index_lse64": (c_int, [c_void_p, c_void_p, c_int, c_int64, ctypes.c_double, c_void_p, c_void_p, c_void_p,
                                     c_void_p]),
+        "clm_index_search_above": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_int, c_void_p]),
+        "clm_index_search_above_rows": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int, c_void_p]),
+        "clm_index_search_above_read": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
         "clm_index_stats": (c_int, [c_void_p, POINTER(c_int64), POINTER(c_int64), POINTER(c_int64)]),
         "clm_index_stats2": (c_int, [c_void_p, POINTER(c_int64), c_int]),
         "clm_cosine_scores": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p]),
@@ -170,6 +173,7 @@ EXPORTED = (
     "clm_index_lse", "clm_index_lse64", "clm_index_remove", "clm_index_update",
     "clm_text_plan", "clm_gemm_attn",
     "clm_layernorm_ex", "clm_gemm_ex", "clm_patchify", "clm_write_cls", "clm_gather_pooled", "clm_pool_project",
+    "clm_index_search_above", "clm_index_search_above_rows", "clm_index_search_above_read",
 )
 CLM_EPI_STORE, CLM_EPI_GELU, CLM_EPI_RESID, CLM_EPI_SCORE = 0, 1, 2, 4
 CLM_EPI_PATCH = 3   # clm_gemm_ex only

@@ -40,7 +40,8 @@ int clm_index_destroy(clm_index* x) {
   DeviceGuard g(x->dev);
   (void)hipDeviceSynchronize();
   for (void* p : {(void*)x->rows, (void*)x->inv, (void*)x->rows32, x->ws, x->ws2, x->ws3, x->ws4, (void*)x->samp,
-                  (void*)x->samp_inv, (void*)x->inv_keys, x->mut})
+                  (void*)x->samp_inv, (void*)x->inv_keys, x->mut, (void*)x->res_s, (void*)x->res_i, (void*)x->rg_comp,
+                  (void*)x->rg_comp2, x->rg_items})
     if (p) (void)hipFree(p);
   delete x;
   return CLM_OK;
@@ -104,6 +105,7 @@ int clm_index_append(clm_index* x, const void* rows, int dtype, int64_t n, void*
   if (r) return r;
   x->samp_n = -1;   // the threshold sample is rebuilt from the new row set
   x->inv_keys_n = -1;
+  x->res_valid = false;   // a held threshold-search result describes the previous rows
   if (dtype == CLM_F32 && !x->rows32 && (r = start_rows32(x, st))) return r;
   const size_t bytes = (size_t)n * x->dim * dtype_size(dtype);
   const void* src = rows;
@@ -172,6 +174,7 @@ int clm_index_import(clm_index* x, const uint16_t* rows16, const float* inv, con
   if (r) return r;
   x->samp_n = -1;
   x->inv_keys_n = -1;
+  x->res_valid = false;   // a held threshold-search result describes the previous rows
   const size_t cnt = (size_t)n * x->dim;
   if (rows32 && !x->rows32 && (r = start_rows32(x, st))) return r;
   u16* d16 = x->rows + (size_t)x->n * x->dim;
@@ -194,6 +197,7 @@ int clm_index_reset(clm_index* x) {
   x->n = 0;
   x->samp_n = -1;   // never reuse a sample of the previous rows
   x->inv_keys_n = -1;
+  x->res_valid = false;   // a held threshold-search result describes the previous rows
   return CLM_OK;
 }
 
@@ -256,6 +260,7 @@ int clm_index_remove(clm_index* x, const int64_t* ids, int64_t n_ids, void* stre
   if ((r = mutate_stage(x))) return r;
   x->samp_n = -1;
   x->inv_keys_n = -1;
+  x->res_valid = false;   // a held threshold-search result describes the previous rows
   int64_t* drem = nullptr;   // the sorted list on the device, for the gather's binary search
   if (hipMalloc(&drem, (size_t)m * 8) != hipSuccess) {
     (void)hipGetLastError();
@@ -321,6 +326,7 @@ int clm_index_update(clm_index* x, const int64_t* ids, const void* rows, int dty
   if (dtype == CLM_F32 && !x->rows32 && (r = start_rows32(x, st))) return r;
   x->samp_n = -1;   // n stays: nothing else would rebuild the sample and the order keys
   x->inv_keys_n = -1;
+  x->res_valid = false;   // a held threshold-search result describes the previous rows
   // per batch of B rows, in the staging buffer: the rows as given (when they come from the host or
   // are not 16-byte aligned), their fp16 operands, their fp32 form (f16 rows into an index with the
   // fp32 copy), the local ids, the inverse norms -- converted by append's own routines, then scattered
@@ -396,11 +402,12 @@ int clm_index_stats(const clm_index* x, int64_t* filtered, int64_t* exact, int64
 
 int clm_index_stats2(const clm_index* x, int64_t* out, int n) {
   if (!x || !out || n < 0) return fail(CLM_E_ARG, "bad argument");
-  const int64_t v[14] = {x->search_stats[0], x->search_stats[3], x->search_stats[1], x->search_stats[2],
+  const int64_t v[17] = {x->search_stats[0], x->search_stats[3], x->search_stats[1], x->search_stats[2],
                          x->search_stats[4], x->search_stats[5], x->search_stats[6], x->search_stats[7],
                          x->search_stats[8], x->search_stats[9], x->search_stats[10], x->search_stats[11],
-                         x->search_stats[12], x->search_stats[13]};
-  for (int i = 0; i < n && i < 14; ++i) out[i] = v[i];
+                         x->search_stats[12], x->search_stats[13], x->search_stats[14], x->search_stats[15],
+                         x->search_stats[16]};
+  for (int i = 0; i < n && i < 17; ++i) out[i] = v[i];
   return CLM_OK;
 }
 

@@ -102,5 +102,15 @@ struct clm_index {
   // whose band list overflowed its capacity, [10]: band rows re-scored for the queries of [7]
   // [11] / [12]: log-sum-exp queries served by the EPI_LSE pass / by the exact route, [13]: queries
   // whose EPI_LSE band list overflowed its capacity
-  int64_t search_stats[14] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  // [14] / [15]: threshold-search queries served by the EPI_FILTER pass / by the exact route, [16]:
+  // those whose candidate list overflowed its capacity
+  int64_t search_stats[17] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  // The held result of the last threshold search (clm_index_search_above / _rows): res_n entries
+  // (exact score, global id) in CSR order, read by clm_index_search_above_read until the next
+  // threshold search, reset, mutation or destroy (res_valid). rg_comp / rg_comp2: the composites it
+  // is built from (the segmented sort's two buffers), rg_items: the sort / merge / decode work items.
+  float* res_s = nullptr; int64_t* res_i = nullptr; int64_t res_cap = 0, res_n = 0; bool res_valid = false;
+  uint64_t* rg_comp = nullptr; int64_t rg_comp_cap = 0;
+  uint64_t* rg_comp2 = nullptr; int64_t rg_comp2_cap = 0;
+  void* rg_items = nullptr; size_t rg_items_bytes = 0;
 };

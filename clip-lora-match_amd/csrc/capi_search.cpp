@@ -1096,4 +1096,429 @@ int clm_index_lse64(clm_index* x, const void* q, int q_dtype, int64_t nq, double
   return CLM_OK;
 }
 
+// ---- threshold search (clm_index_search_above / _rows / _read) -------------------------------
+// result(q) = the rows (s, id) with rank_ahead(s, id, tau[q], INT64_MAX): exact score s >= tau[q],
+// NaN above every number, in the search order. The fast route lists, per query, every row whose
+// fp16-pass score reaches theta = tau - RANK_MARGIN (EPI_FILTER): tau is exact and only the fp16-pass
+// score carries error, the case RANK_MARGIN's comment bounds, so a row with s >= tau is always
+// listed. The listed rows are re-scored exactly (lse_band_scores), those that pass are counted,
+// placed and emitted as composites; the exact route takes them from windows of exact scores. Either
+// way a query owns one segment of x->rg_comp, and range_finish sorts the segments and decodes them
+// into the held result in CSR order. Both routes compare exact_cos scores against the same tau, so
+// the result does not depend on the route.
+struct RangeBuild {   // where each query's segment lies in x->rg_comp
+  std::vector<int64_t> src, len;
+  int64_t total = 0;
+  void place(int64_t q, int64_t n) { src[q] = total; len[q] = n; total += n; }
+};
+
+// room for `need` composites in x->rg_comp, the first `used` kept; amortised as the index rows are
+static int range_reserve(clm_index* x, int64_t used, int64_t need, hipStream_t st) {
+  if (need <= x->rg_comp_cap) return CLM_OK;
+  HIPCHK(hipStreamSynchronize(st));
+  int64_t nc = std::max<int64_t>(std::max<int64_t>(need, 2 * x->rg_comp_cap), 1 << 16);
+  uint64_t* p = nullptr;
+  if (hipMalloc(&p, (size_t)nc * 8) != hipSuccess) {
+    (void)hipGetLastError();
+    nc = need;
+    if (hipMalloc(&p, (size_t)nc * 8) != hipSuccess) {
+      (void)hipGetLastError();
+      return fail(CLM_E_OOM, "threshold search: a result of " + std::to_string(need) + " entries cannot be allocated");
+    }
+  }
+  hipError_t e = used > 0 ? hipMemcpyAsync(p, x->rg_comp, (size_t)used * 8, hipMemcpyDeviceToDevice, st) : hipSuccess;
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) {
+    (void)hipFree(p);
+    return fail(CLM_E_HIP, std::string("threshold search: ") + hipGetErrorString(e));
+  }
+  if (x->rg_comp) (void)hipFree(x->rg_comp);
+  x->rg_comp = p;
+  x->rg_comp_cap = nc;
+  return CLM_OK;
+}
+
+// the per-query buffers of one filter pass over nb queries with `cap` list slots each
+struct RangeBufs {
+  size_t o_cnt, o_len, o_cur, o_plan, o_src, o_band, o_bs;
+  void take(Layout& lay, int64_t nb, int64_t cap) {
+    o_cnt = lay.take((size_t)nb * 4); o_len = lay.take((size_t)nb * 4); o_cur = lay.take((size_t)nb * 4);
+    o_plan = lay.take((size_t)(nb + 1) * 4); o_src = lay.take((size_t)nb * 8);
+    o_band = lay.take((size_t)nb * cap * 8); o_bs = lay.take((size_t)nb * cap * 4);
+  }
+};
+
+// One filter pass for nb queries (global query numbers qid[0, nb)): EPI_FILTER lists the rows at or
+// above theta (their fp16-pass scores go to band_s, which lse_band_scores then overwrites with the
+// exact ones), range_keep_count counts the rows that pass, the counts come to the host and place the
+// segments, range_emit fills them. Queries whose list exceeded `cap` go to over / ocount.
+static int range_pass(clm_index* x, const unsigned* keys, const u16* q16, const float* qinv, const float* q32,
+                      const double* qn, const float* tau, const float* theta, int64_t nb, int64_t cap, int cfg,
+                      uint8_t* w, const RangeBufs& b, const int64_t* qid, RangeBuild& rb, std::vector<int64_t>& over,
+                      std::vector<int64_t>& ocount, hipStream_t st) {
+  int* cnt = (int*)(w + b.o_cnt);
+  int* len = (int*)(w + b.o_len);
+  int* cursor = (int*)(w + b.o_cur);
+  int* plan = (int*)(w + b.o_plan);
+  int64_t* src = (int64_t*)(w + b.o_src);
+  int64_t* band = (int64_t*)(w + b.o_band);
+  float* band_s = (float*)(w + b.o_bs);
+  const ExactRows xr = exact_rows(x);
+  HIPCHK(hipMemsetAsync(cnt, 0, (size_t)nb * 4, st));
+  HIPCHK(hipMemsetAsync(len, 0, (size_t)nb * 4, st));
+  HIPCHK(hipMemsetAsync(cursor, 0, (size_t)nb * 4, st));
+  GemmArgs gf = index_pass(x, q16, qinv, nb, theta, cnt, band, cap);
+  gf.cand_s = band_s;
+  gf.cbound = keys;
+  KCHK(gemm_cfg(false, EPI_FILTER, cfg, gf, st));
+  KCHK(lse_band_scores(band, cnt, cap, q32, qn, (int)x->dim, xr.p, xr.f16, x->offset, nb, plan, band_s, st));
+  KCHK(range_keep_count(band_s, band, cnt, cap, plan, tau, nb, len, st));
+  std::vector<int> hcnt(nb), hlen(nb);
+  HIPCHK(hipMemcpyAsync(hcnt.data(), cnt, (size_t)nb * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(hlen.data(), len, (size_t)nb * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  std::vector<int64_t> hsrc(nb, 0);
+  const int64_t used = rb.total;
+  for (int64_t i = 0; i < nb; ++i) {
+    if (hcnt[i] > cap) {
+      over.push_back(qid[i]);
+      ocount.push_back(hcnt[i]);
+    } else {
+      hsrc[i] = rb.total;
+      rb.place(qid[i], hlen[i]);
+    }
+  }
+  if (rb.total == used) return CLM_OK;
+  if (int r = range_reserve(x, used, rb.total, st)) return r;
+  HIPCHK(hipMemcpyAsync(src, hsrc.data(), (size_t)nb * 8, hipMemcpyHostToDevice, st));
+  KCHK(range_emit(band_s, band, cnt, cap, plan, tau, x->offset, nb, len, cursor, src, x->rg_comp, st));
+  HIPCHK(hipStreamSynchronize(st));   // hsrc goes out of scope; the next pass rewrites the buffers
+  return CLM_OK;
+}
+
+// The exact route for nq queries (global query numbers qid[0, nq), or 0 .. nq - 1): one walk of the
+// row windows with count_rank (g = INT64_MAX) gives the lengths, a second one collects each
+// window's passing (score, row) composites at the query's cursor.
+static int range_exact(clm_index* x, const float* q32, const double* qn, const float* tau, int64_t nq,
+                       const int64_t* qid, RangeBuild& rb, hipStream_t st) {
+  const int dim = (int)x->dim;
+  Layout hl;
+  const size_t o_g = hl.take((size_t)nq * 8), o_ab = hl.take((size_t)nq * 8), o_cur = hl.take((size_t)nq * 8),
+               o_end = hl.take((size_t)nq * 8);
+  ExactWindows w;
+  int r = exact_windows(x, nq, 4, hl.total(), &w);
+  if (r) return r;
+  float* sc = (float*)w.sc;
+  int64_t* g = (int64_t*)(w.header + o_g);
+  int64_t* above = (int64_t*)(w.header + o_ab);
+  int64_t* cursor = (int64_t*)(w.header + o_cur);
+  int64_t* end = (int64_t*)(w.header + o_end);
+  std::vector<int64_t> hg(nq, INT64_MAX), hab(nq), hcur(nq), hend(nq);
+  HIPCHK(hipMemcpyAsync(g, hg.data(), (size_t)nq * 8, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemsetAsync(above, 0, (size_t)nq * 8, st));
+  r = walk_exact_windows(x, w, nq, [&](int64_t q0, int64_t nb, int64_t r0, int64_t rn, ExactRows er) -> int {
+    KCHK(exact_scores(q32 + q0 * dim, qn + q0, nb, er.p, er.f16, rn, dim, sc, w.ch, st));
+    KCHK(count_rank(sc, w.ch, nb, rn, x->offset + r0, tau + q0, g + q0, above + q0, st));
+    return CLM_OK;
+  });
+  if (r) return r;
+  HIPCHK(hipMemcpyAsync(hab.data(), above, (size_t)nq * 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  const int64_t used = rb.total;
+  for (int64_t i = 0; i < nq; ++i) {
+    hcur[i] = rb.total;
+    rb.place(qid ? qid[i] : i, hab[i]);
+    hend[i] = rb.total;
+  }
+  if (rb.total == used) return CLM_OK;
+  if ((r = range_reserve(x, used, rb.total, st))) return r;
+  HIPCHK(hipMemcpyAsync(cursor, hcur.data(), (size_t)nq * 8, hipMemcpyHostToDevice, st));
+  HIPCHK(hipMemcpyAsync(end, hend.data(), (size_t)nq * 8, hipMemcpyHostToDevice, st));
+  r = walk_exact_windows(x, w, nq, [&](int64_t q0, int64_t nb, int64_t r0, int64_t rn, ExactRows er) -> int {
+    KCHK(exact_scores(q32 + q0 * dim, qn + q0, nb, er.p, er.f16, rn, dim, sc, w.ch, st));
+    KCHK(range_collect(sc, w.ch, nb, rn, r0, tau + q0, cursor + q0, end + q0, x->rg_comp, st));
+    return CLM_OK;
+  });
+  if (r) return r;
+  HIPCHK(hipStreamSynchronize(st));   // the host arrays go out of scope
+  return CLM_OK;
+}
+
+// The fast route. Blocks are cut by band_query_block on the list bytes (12 B per slot): the block
+// shrinks, never the capacity. `skip` marks the queries the exact route must serve whatever their
+// list holds (theta = +inf keeps their lists empty). Overflowed lists are redone with a capacity of
+// count + count / 8 + 256, gathered and grouped as overflow_wide does within the same 1 GiB; a list
+// that overflows again (or would not fit) is appended to `exact`.
+static int range_band(clm_index* x, const unsigned* keys, const QueryStage& qs, const float* tau, const float* theta,
+                      int64_t nq, int64_t cap, RangeBuild& rb, std::vector<int64_t>& exact, int64_t& overflowed,
+                      hipStream_t st) {
+  const int dim = (int)x->dim;
+  const int64_t N = x->n;
+  int r;
+  std::vector<int64_t> over, ocount, ids(nq);
+  for (int64_t i = 0; i < nq; ++i) ids[i] = i;
+  {
+    const int64_t nqb = band_query_block(nq, cap * 12, 1);
+    Layout lay;
+    RangeBufs b;
+    b.take(lay, nqb, cap);
+    if ((r = grow(&x->ws2, &x->ws2_bytes, lay.total()))) return r;
+    for (int64_t q0 = 0; q0 < nq; q0 += nqb) {
+      const int64_t nb = std::min(nqb, nq - q0);
+      if ((r = range_pass(x, keys, qs.q16 + q0 * dim, qs.qinv + q0, qs.q32 + q0 * dim, qs.qn + q0, tau + q0,
+                          theta + q0, nb, cap, -1, (uint8_t*)x->ws2, b, ids.data() + q0, rb, over, ocount, st)))
+        return r;
+    }
+  }
+  overflowed = (int64_t)over.size();
+  if (over.empty()) return CLM_OK;
+  std::vector<int64_t> wide;
+  int64_t cap_max = 0;
+  for (size_t j = 0; j < over.size(); ++j) {
+    const int64_t cap2 = std::min<int64_t>(N, ocount[j] + ocount[j] / 8 + 256);
+    if (cap2 * 12 <= ((int64_t)1 << 30)) {
+      wide.push_back(over[j]);
+      cap_max = std::max(cap_max, cap2);
+    } else {
+      exact.push_back(over[j]);
+    }
+  }
+  if (wide.empty()) return CLM_OK;
+  const int64_t n = (int64_t)wide.size();
+  const int64_t G = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(n, 4096), ((int64_t)1 << 30) / (cap_max * 12)));
+  Layout lay;
+  const size_t p_x = lay.take((size_t)G * 8), p_q16 = lay.take((size_t)G * dim * 2), p_qi = lay.take((size_t)G * 4),
+               p_q32 = lay.take((size_t)G * dim * 4), p_qn = lay.take((size_t)G * 8), p_th = lay.take((size_t)G * 4),
+               p_tau = lay.take((size_t)G * 4);
+  RangeBufs b;
+  b.take(lay, G, cap_max);
+  if ((r = grow(&x->ws4, &x->ws4_bytes, lay.total()))) return r;
+  uint8_t* w = (uint8_t*)x->ws4;
+  int64_t* gx = (int64_t*)(w + p_x);
+  for (int64_t g0 = 0; g0 < n; g0 += G) {
+    const int64_t ng = std::min(G, n - g0);
+    HIPCHK(hipMemcpyAsync(gx, wide.data() + g0, (size_t)ng * 8, hipMemcpyHostToDevice, st));
+    KCHK(gather_rows(qs.q16, (int64_t)dim * 2, gx, ng, (int64_t)dim * 2, w + p_q16, (int64_t)dim * 2, false, st));
+    KCHK(gather_rows(qs.qinv, 4, gx, ng, 4, w + p_qi, 4, false, st));
+    KCHK(gather_rows(qs.q32, (int64_t)dim * 4, gx, ng, (int64_t)dim * 4, w + p_q32, (int64_t)dim * 4, false, st));
+    KCHK(gather_rows(qs.qn, 8, gx, ng, 8, w + p_qn, 8, false, st));
+    KCHK(gather_rows(theta, 4, gx, ng, 4, w + p_th, 4, false, st));
+    KCHK(gather_rows(tau, 4, gx, ng, 4, w + p_tau, 4, false, st));
+    // these lists overflowed: appends dominate the pass, gemm_kernel's 256 x 256 FILTER epilogue
+    // (overflow_wide's choice)
+    static const int ocfg = getenv("CLM_GEMM_CFG") ? -1 : 1;
+    std::vector<int64_t> ocount2;
+    if ((r = range_pass(x, keys, (const u16*)(w + p_q16), (const float*)(w + p_qi), (const float*)(w + p_q32),
+                        (const double*)(w + p_qn), (const float*)(w + p_tau), (const float*)(w + p_th), ng, cap_max,
+                        ocfg, w, b, wide.data() + g0, rb, exact, ocount2, st)))
+      return r;   // range_pass drains the stream: gx may be rewritten
+  }
+  return CLM_OK;
+}
+
+// Segmented sort of the placed segments and the decode into the held result, in CSR order.
+static int range_finish(clm_index* x, const RangeBuild& rb, int64_t nq, int64_t* out_offsets, hipStream_t st) {
+  std::vector<int64_t> off(nq + 1, 0);
+  for (int64_t q = 0; q < nq; ++q) off[q + 1] = off[q] + rb.len[q];
+  const int64_t total = off[nq];
+  // work items: LDS runs, merge chunks of the segments longer than one run, decode chunks (the
+  // short segments from the first buffer, the long ones from wherever the last merge pass left them)
+  constexpr int64_t DECODE_CHUNK = 4096;
+  std::vector<RangeItem> runs, merges, dec_a, dec_b;
+  int64_t longest = 0, longest_run = 0;
+  for (int64_t q = 0; q < nq; ++q) {
+    const int64_t n = rb.len[q], s0 = rb.src[q];
+    if (n <= 0) continue;
+    const bool is_long = n > RANGE_RUN;
+    for (int64_t a = 0; a < n; a += RANGE_RUN) {
+      const int64_t m = std::min<int64_t>(RANGE_RUN, n - a);
+      if (m >= 2) runs.push_back(RangeItem{s0 + a, 0, m});
+      longest_run = std::max(longest_run, m);
+    }
+    if (is_long) {
+      longest = std::max(longest, n);
+      for (int64_t a = 0; a < n; a += RANGE_MERGE_CHUNK) merges.push_back(RangeItem{s0, a, n});
+    }
+    for (int64_t a = 0; a < n; a += DECODE_CHUNK)
+      (is_long ? dec_b : dec_a).push_back(RangeItem{s0 + a, off[q] + a, std::min<int64_t>(DECODE_CHUNK, n - a)});
+  }
+  if (total > 0) {
+    if (total > x->res_cap) {   // the held result's own arrays, 12 B per entry, amortised as the index rows are
+      HIPCHK(hipStreamSynchronize(st));
+      float* ns = nullptr;
+      int64_t* ni = nullptr;
+      auto alloc = [&](int64_t rows) {
+        if (hipMalloc(&ns, (size_t)rows * 4) == hipSuccess && hipMalloc(&ni, (size_t)rows * 8) == hipSuccess) return true;
+        (void)hipGetLastError();
+        if (ns) (void)hipFree(ns);
+        ns = nullptr; ni = nullptr;
+        return false;
+      };
+      int64_t nc = std::max<int64_t>(total, 2 * x->res_cap);
+      if (!alloc(nc)) {
+        nc = total;
+        if (!alloc(nc))
+          return fail(CLM_E_OOM, "threshold search: a result of " + std::to_string(total) + " entries cannot be allocated");
+      }
+      if (x->res_s) (void)hipFree(x->res_s);
+      if (x->res_i) (void)hipFree(x->res_i);
+      x->res_s = ns; x->res_i = ni; x->res_cap = nc;
+      x->res_valid = false;
+    }
+    if (longest > 0 && x->rg_comp2_cap < x->rg_comp_cap) {   // the merge passes' second buffer
+      HIPCHK(hipStreamSynchronize(st));
+      if (x->rg_comp2) (void)hipFree(x->rg_comp2);
+      x->rg_comp2 = nullptr; x->rg_comp2_cap = 0;
+      if (hipMalloc(&x->rg_comp2, (size_t)x->rg_comp_cap * 8) != hipSuccess) {
+        (void)hipGetLastError();
+        x->rg_comp2 = nullptr;
+        return fail(CLM_E_OOM, "threshold search: a result of " + std::to_string(total) + " entries cannot be sorted");
+      }
+      x->rg_comp2_cap = x->rg_comp_cap;
+    }
+    const size_t isz = sizeof(RangeItem);
+    Layout lay;
+    const size_t o_runs = lay.take(runs.size() * isz), o_mer = lay.take(merges.size() * isz),
+                 o_da = lay.take(dec_a.size() * isz), o_db = lay.take(dec_b.size() * isz);
+    if (int r = grow(&x->rg_items, &x->rg_items_bytes, lay.total(), "threshold search work items")) return r;
+    uint8_t* w = (uint8_t*)x->rg_items;
+    auto up = [&](size_t o, const std::vector<RangeItem>& v) {
+      return v.empty() ? hipSuccess : hipMemcpyAsync(w + o, v.data(), v.size() * isz, hipMemcpyHostToDevice, st);
+    };
+    HIPCHK(up(o_runs, runs));
+    HIPCHK(up(o_mer, merges));
+    HIPCHK(up(o_da, dec_a));
+    HIPCHK(up(o_db, dec_b));
+    x->res_valid = false;   // the held result is rewritten from here on
+    KCHK(range_sort_runs(x->rg_comp, (const RangeItem*)(w + o_runs), (int64_t)runs.size(), longest_run, st));
+    uint64_t *a = x->rg_comp, *b2 = x->rg_comp2;
+    for (int64_t L = RANGE_RUN; L < longest; L <<= 1) {
+      KCHK(range_merge(a, b2, (const RangeItem*)(w + o_mer), (int64_t)merges.size(), L, st));
+      std::swap(a, b2);
+    }
+    KCHK(range_decode(x->rg_comp, (const RangeItem*)(w + o_da), (int64_t)dec_a.size(), x->offset, x->res_s, x->res_i, st));
+    KCHK(range_decode(a, (const RangeItem*)(w + o_db), (int64_t)dec_b.size(), x->offset, x->res_s, x->res_i, st));
+  }
+  if (is_device_ptr(out_offsets)) HIPCHK(hipMemcpyAsync(out_offsets, off.data(), (size_t)(nq + 1) * 8, hipMemcpyHostToDevice, st));
+  else std::memcpy(out_offsets, off.data(), (size_t)(nq + 1) * 8);
+  HIPCHK(hipStreamSynchronize(st));   // the host vectors go out of scope; workspaces are reused by the next call
+  x->res_n = total;
+  x->res_valid = true;
+  return CLM_OK;
+}
+
+// Router, as rank_run's: the whole call takes the exact route for a zero or non-finite inverse norm
+// in the index, dim > MARGIN_MAX_DIM, N > 2^31 - 1, nq x N <= 2^24 (unless CLM_RANK_BAND /
+// $CLM_SEARCH_BOUNDED=1), CLM_RANK_EXACT or $CLM_SEARCH_FULL=1; single queries do when their list
+// overflows twice, when tau is not finite, or when the query's norm is zero, non-finite or outside
+// [1e-30, 1e30] (its fp16 operand is then not a unit row and its exact scores may be NaN, which the
+// fp16 pass never lists).
+static int range_run(clm_index* x, const void* q, int q_dtype, int64_t nq, const float* threshold,
+                     int64_t* out_offsets, int band_cap, void* stream) {
+  if (q_dtype != CLM_F32 && q_dtype != CLM_F16) return fail(CLM_E_ARG, "queries must be f32 or f16");
+  if (x->n == 0) return fail(CLM_E_ARG, "the index is empty");
+  if (x->n > 0xFFFFFFFFll) return fail(CLM_E_ARG, "threshold search: at most 2^32 - 1 rows per index");
+  DeviceGuard guard(x->dev);
+  hipStream_t st = (hipStream_t)stream;
+  RangeBuild rb;
+  rb.src.assign(nq, 0);
+  rb.len.assign(nq, 0);
+  if (nq == 0) return range_finish(x, rb, 0, out_offsets, st);
+  const int dim = (int)x->dim;
+  const int64_t N = x->n;
+  std::vector<float> htau(nq), hth(nq);
+  if (is_device_ptr(threshold)) {
+    HIPCHK(hipMemcpyAsync(htau.data(), threshold, (size_t)nq * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+  } else {
+    std::memcpy(htau.data(), threshold, (size_t)nq * 4);
+  }
+  Layout lay;
+  const size_t o_tau = lay.take((size_t)nq * 4), o_th = lay.take((size_t)nq * 4);
+  QueryStage qs;
+  int r = stage_queries(x, q, q_dtype, nq, lay.total(), st, &qs);
+  if (r) return r;
+  float* tau = (float*)(qs.extra + o_tau);
+  float* theta = (float*)(qs.extra + o_th);
+  HIPCHK(hipMemcpyAsync(tau, htau.data(), (size_t)nq * 4, hipMemcpyHostToDevice, st));
+  std::vector<double> hqn(nq);
+  HIPCHK(hipMemcpyAsync(hqn.data(), qs.qn, (size_t)nq * 8, hipMemcpyDeviceToHost, st));
+  const unsigned* keys = nullptr;
+  bool inv_ok = false;
+  if ((r = inv_norms_finite(x, st, &inv_ok, &keys))) return r;   // drains the stream
+  const int flags = band_cap > 0 ? band_cap & (CLM_RANK_EXACT | CLM_RANK_BAND) : 0;
+  const char* e_full = getenv("CLM_SEARCH_FULL");
+  const char* e_bounded = getenv("CLM_SEARCH_BOUNDED");
+  const bool force_exact = (flags & CLM_RANK_EXACT) || (e_full && atoi(e_full));
+  const bool force_band = (flags & CLM_RANK_BAND) || (e_bounded && atoi(e_bounded));
+  const bool all_exact = force_exact || !inv_ok || dim > MARGIN_MAX_DIM || N > 0x7FFFFFFF ||
+                         (!force_band && (double)nq * (double)N <= (double)(1 << 24));
+  int64_t n_fast = 0, n_exact = nq, n_over = 0;
+  if (all_exact) {
+    if ((r = range_exact(x, qs.q32, qs.qn, tau, nq, nullptr, rb, st))) return r;
+  } else {
+    std::vector<int64_t> exact;
+    for (int64_t i = 0; i < nq; ++i) {
+      const bool q_ok = hqn[i] >= 1e-30 && hqn[i] <= 1e30;
+      if (q_ok && std::fabs(htau[i]) <= 3.4028235e38f) {
+        hth[i] = htau[i] - RANK_MARGIN;
+      } else {
+        hth[i] = INFINITY;   // lists nothing: the exact route serves the query
+        exact.push_back(i);
+      }
+    }
+    HIPCHK(hipMemcpyAsync(theta, hth.data(), (size_t)nq * 4, hipMemcpyHostToDevice, st));
+    if ((r = stage_queries_f16(x, qs, nq, st))) return r;
+    if ((r = range_band(x, keys, qs, tau, theta, nq, band_capacity(band_cap, N), rb, exact, n_over, st))) return r;
+    n_exact = (int64_t)exact.size();
+    n_fast = nq - n_exact;
+    // their queries, norms and thresholds gathered; one exact pass places and fills their segments
+    r = redo_subset(x, exact, {{qs.q32, (int64_t)dim * 4}, {qs.qn, 8}, {tau, 4}}, {}, "threshold search", st,
+                    [&](void* const* in, void* const*) -> int {
+                      return range_exact(x, (const float*)in[0], (const double*)in[1], (const float*)in[2],
+                                         (int64_t)exact.size(), exact.data(), rb, st);
+                    });
+    if (r) return r;
+  }
+  if ((r = range_finish(x, rb, nq, out_offsets, st))) return r;
+  x->search_stats[14] += n_fast;
+  x->search_stats[15] += n_exact;
+  x->search_stats[16] += n_over;
+  return CLM_OK;
+}
+
+int clm_index_search_above(clm_index* x, const void* q, int q_dtype, int64_t nq, const float* threshold,
+                           int64_t* out_offsets, int band_cap, void* stream) {
+  if (!x || nq < 0 || !out_offsets || (nq > 0 && (!q || !threshold))) return fail(CLM_E_ARG, "bad argument");
+  return range_run(x, q, q_dtype, nq, threshold, out_offsets, band_cap, stream);
+}
+
+int clm_index_search_above_rows(clm_index* x, int64_t row0, int64_t nrows, const float* threshold,
+                                int64_t* out_offsets, int band_cap, void* stream) {
+  if (!x || nrows < 0 || !out_offsets || (nrows > 0 && !threshold)) return fail(CLM_E_ARG, "bad argument");
+  if (x->n == 0) return fail(CLM_E_ARG, "the index is empty");
+  if (row0 < x->offset || row0 - x->offset > x->n || nrows > x->n - (row0 - x->offset))
+    return fail(CLM_E_ARG, "rows [" + std::to_string(row0) + ", " + std::to_string(row0) + " + " + std::to_string(nrows) +
+                               ") are outside the index [" + std::to_string(x->offset) + ", " +
+                               std::to_string(x->offset + x->n) + ")");
+  const ExactRows er = exact_rows(x, row0 - x->offset);   // the queries stay where they are, in HBM
+  return range_run(x, er.p, er.f16 ? CLM_F16 : CLM_F32, nrows, threshold, out_offsets, band_cap, stream);
+}
+
+int clm_index_search_above_read(clm_index* x, int64_t start, int64_t n, float* out_scores, int64_t* out_idx,
+                                void* stream) {
+  if (!x || (n > 0 && (!out_scores || !out_idx))) return fail(CLM_E_ARG, "bad argument");
+  if (!x->res_valid) return fail(CLM_E_STATE, "no threshold-search result is held (none yet, or the index changed since)");
+  if (start < 0 || n < 0 || start > x->res_n || n > x->res_n - start)
+    return fail(CLM_E_STATE, "entries [" + std::to_string(start) + ", " + std::to_string(start) + " + " +
+                                 std::to_string(n) + ") are outside the held result of " + std::to_string(x->res_n));
+  if (n == 0) return CLM_OK;
+  DeviceGuard guard(x->dev);
+  hipStream_t st = (hipStream_t)stream;
+  HIPCHK(copy_out(out_scores, x->res_s + start, (size_t)n * 4, st));
+  HIPCHK(copy_out(out_idx, x->res_i + start, (size_t)n * 8, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return CLM_OK;
+}
+
 }  // extern "C"

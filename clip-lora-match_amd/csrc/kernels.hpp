@@ -338,6 +338,41 @@ hipError_t lse_finish(const float* band_s, const int* cnt, int64_t cap, const fl
                       const float* theta, double scale, double E, int64_t N, int64_t nq, double* lse, float* err,
                       int* redo, hipStream_t s);
 
+// ----------------------------------------------------------- threshold search (k_range.hip) ---
+// The result of query q under threshold tau[q]: the rows (s, id) with rank_ahead(s, id, tau[q],
+// INT64_MAX) -- s >= tau, NaN above every number -- as 64-bit composites (float_key(s) << 32 |
+// 0xFFFFFFFF - local row; descending composites = score desc, id asc) in one segment per query.
+// A work item of the sort / merge / decode launches, cut by the host from the segment lengths:
+//   range_sort_runs: the run of n composites (2 <= n <= RANGE_RUN) at `start`;
+//   range_merge:     elements [aux, aux + RANGE_MERGE_CHUNK) of the segment of n composites at `start`;
+//   range_decode:    n composites at `start` -> entries [aux, aux + n) of the result.
+struct RangeItem { int64_t start, aux, n; };
+constexpr int RANGE_RUN = 8192, RANGE_MERGE_CHUNK = 1024, RANGE_GRID = 4096;
+// keep / count over the re-scored candidate lists (band [nq, cap] global ids beside their exact scores
+// band_s, cnt[q] entries, complete lists only; plan: rescore_plan's items, as lse_band_scores leaves
+// them): len[q] (zeroed by the caller) += the listed rows that pass
+hipError_t range_keep_count(const float* band_s, const int64_t* band, const int* cnt, int64_t cap, const int* plan,
+                            const float* tau, int64_t nq, int* len, hipStream_t s);
+// emit: those rows' composites (local row = id - offset) into seg[src[q] ..), len[q] of them, slots from
+// cursor[q] (zeroed by the caller; integer atomics: the order inside a segment is not defined)
+hipError_t range_emit(const float* band_s, const int64_t* band, const int* cnt, int64_t cap, const int* plan,
+                      const float* tau, int64_t offset, int64_t nq, int* len, int* cursor, const int64_t* src,
+                      uint64_t* seg, hipStream_t s);
+// window collect (the exact route): the passing entries of a window of exact scores [nq, C] (row
+// stride lds; column j = local row r0 + j, r0 + C <= 2^32 - 1) appended at seg[cursor[q]++], never at
+// or past end[q]
+hipError_t range_collect(const float* scores, int64_t lds, int64_t nq, int64_t C, int64_t r0, const float* tau,
+                         int64_t* cursor, const int64_t* end, uint64_t* seg, hipStream_t s);
+// segmented sort, descending: every item's run sorted in LDS by one workgroup (longest: the largest
+// item's n), then for the segments longer than one run log2 passes of range_merge with L = RANGE_RUN,
+// 2 RANGE_RUN, ... between two buffers (a pass moves every element of its items' segments to dst)
+hipError_t range_sort_runs(uint64_t* seg, const RangeItem* items, int64_t nitems, int64_t longest, hipStream_t s);
+hipError_t range_merge(const uint64_t* src, uint64_t* dst, const RangeItem* items, int64_t nitems, int64_t L,
+                       hipStream_t s);
+// composites -> (exact score, global id = offset + local row)
+hipError_t range_decode(const uint64_t* seg, const RangeItem* items, int64_t nitems, int64_t offset, float* out_s,
+                        int64_t* out_i, hipStream_t s);
+
 // ----------------------------------------------------------- index mutation (k_mutate.hip) ---
 // Whole-row movers over the index's three arrays (fp16 rows, fp32 rows or null, fp32 inverse
 // norms), 16-byte loads and stores. gather_rows: the rows of [s0, s0 + rows) that are not in rem

@@ -126,6 +126,34 @@ def ranges_after_remove(sizes, starts, ids):
     return local, new_sizes, new_starts
 
 
+def merge_ragged(parts):
+    """Merge of the row shards' CosineIndex.search_above results (host function). parts: one
+    (offsets [nq + 1], scores [total], ids [total]) per shard, ids global. Returns the same triple
+    (CPU tensors) for the whole index: each query's entries are the concatenation of the shards'
+    lists, ordered by (score desc, id asc) with NaN above every number -- the order of `search`,
+    so the merged result is what one index over all the rows returns. Shards may be empty."""
+    import numpy as np
+    parts = [tuple(torch.as_tensor(t).detach().cpu() for t in p) for p in parts]
+    if not parts:
+        raise ValueError("one (offsets, scores, ids) triple per shard expected")
+    nq = parts[0][0].numel() - 1
+    qid, sc, ix = [], [], []
+    for off, s, i in parts:
+        if off.numel() != nq + 1 or s.numel() != int(off[-1]) or i.numel() != s.numel():
+            raise ValueError("shard results disagree on the number of queries or entries")
+        qid.append(np.repeat(np.arange(nq, dtype=np.int64), np.diff(off.numpy().astype(np.int64))))
+        sc.append(s.to(torch.float32).numpy())
+        ix.append(i.to(torch.int64).numpy())
+    qid, sc, ix = np.concatenate(qid), np.concatenate(sc), np.concatenate(ix)
+    bits = np.where(np.isnan(sc), sc.view(np.uint32) & np.uint32(0x7FFFFFFF), sc.view(np.uint32))   # any NaN first
+    key = np.where(bits & np.uint32(0x80000000), ~bits, bits | np.uint32(0x80000000)).astype(np.int64)   # float_key
+    order = np.lexsort((ix, -key, qid))
+    counts = np.bincount(qid, minlength=nq) if nq else np.zeros((0,), dtype=np.int64)
+    off = np.zeros((nq + 1,), dtype=np.int64)
+    np.cumsum(counts, out=off[1:])
+    return torch.from_numpy(off), torch.from_numpy(sc[order].copy()), torch.from_numpy(ix[order].copy())
+
+
 class ShardedIndex:
     """Row-sharded cosine index: this rank holds rows [start, stop) of n_total."""
 
@@ -190,6 +218,40 @@ class ShardedIndex:
             return s, i
         s_all, i_all = gather_candidates(s, i, self.group)
         return merge(s_all, i_all, self.world, k)
+
+    def search_above(self, queries: torch.Tensor, threshold):
+        """CosineIndex.search_above over the whole sharded index (a collective call): each rank
+        searches its shard, one gather of the ragged lists follows -- the offsets first (equal
+        sizes), then scores and ids padded to the longest shard result -- and merge_ragged orders
+        every query's concatenation. Returns (offsets, scores, ids), identical on every rank and to
+        one index holding all the rows, on the device of the local result."""
+        if len(self.local) == 0:   # a shard a remove emptied: no entries (an empty index refuses the call)
+            nq = 1 if torch.as_tensor(queries).dim() == 1 else torch.as_tensor(queries).shape[0]
+            dev = getattr(self.local, "device", "cpu")
+            off = torch.zeros((nq + 1,), dtype=torch.int64, device=dev)
+            s = torch.empty((0,), dtype=torch.float32, device=dev)
+            i = torch.empty((0,), dtype=torch.int64, device=dev)
+        else:
+            off, s, i = self.local.search_above(queries, threshold)
+        if self.world == 1:
+            return off, s, i
+        dev = s.device
+        off = off.to(dev).contiguous()
+        offs = torch.empty((self.world * off.numel(),), dtype=torch.int64, device=dev)
+        dist.all_gather_into_tensor(offs, off, group=self.group)
+        offs = offs.view(self.world, -1).cpu()
+        width = max(int(offs[:, -1].max()), 1)
+        sp = torch.zeros((width,), dtype=torch.float32, device=dev)
+        ip = torch.zeros((width,), dtype=torch.int64, device=dev)
+        sp[: s.numel()] = s
+        ip[: i.numel()] = i
+        s_all = torch.empty((self.world * width,), dtype=torch.float32, device=dev)
+        i_all = torch.empty((self.world * width,), dtype=torch.int64, device=dev)
+        dist.all_gather_into_tensor(s_all, sp, group=self.group)
+        dist.all_gather_into_tensor(i_all, ip, group=self.group)
+        s_all, i_all = s_all.view(self.world, width).cpu(), i_all.view(self.world, width).cpu()
+        parts = [(offs[r], s_all[r, : int(offs[r, -1])], i_all[r, : int(offs[r, -1])]) for r in range(self.world)]
+        return tuple(t.to(dev) for t in merge_ragged(parts))
 
 
 def build_index_sharded(encode_rows: Callable[[int, int], torch.Tensor], n_total: int, batch: int,

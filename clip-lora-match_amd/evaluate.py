@@ -104,6 +104,64 @@ def matching_accuracy(image_emb, text_emb) -> float:
     return recall_at_k(retrieval_ranks(image_emb, text_emb), (1,))["recall@1"]
 
 
+# ------------------------------------------------------------------ threshold evaluator --
+def threshold_metrics(counts, n_index: int, k_values: Sequence[int] = (1, 5, 10)) -> Dict:
+    """The aggregation of the reference's second evaluator (scripts/evaluate.py:221-267,
+    evaluate_epoch) from one number per query: counts[i] = how many index rows are relevant to query
+    i. That evaluator calls relevant every row whose cosine is >= a threshold and ranks the index by
+    the same cosines (evaluate_single_query, :158-166), so the relevant set IS A PREFIX of the
+    ranking -- its first counts[i] entries. Hence, per query with c relevant rows,
+      recall@k    = min(c, k) / c      (0 when c = 0; calculate_recall_at_k, :50-58)
+      precision@k = min(c, k) / k      (calculate_precision_at_k, :61-67)
+      mrr = ap    = 1 when c > 0 else 0  (the first hit is at rank 1, every hit r of the prefix has
+                                        precision r / r; calculate_mrr / _average_precision :70-99)
+    and no N-long argsort is needed. Returns the reference's metrics dict without its epoch and
+    timing entries: num_queries, recall / precision {k: percent}, mrr and map as means."""
+    c = counts.detach().cpu().numpy() if isinstance(counts, torch.Tensor) else np.asarray(counts)
+    c = c.astype(np.int64).reshape(-1)
+    if c.size == 0:
+        raise ValueError("no queries: the metrics need at least one")
+    if (c < 0).any() or (c > int(n_index)).any():
+        raise ValueError("a relevant count lies outside [0, n_index]")
+    recall, precision = {}, {}
+    for k in k_values:
+        k = int(k)
+        hit = np.minimum(c, k).astype(np.float64)
+        recall[k] = float(np.mean(np.where(c > 0, hit / np.maximum(c, 1), 0.0)) * 100)
+        precision[k] = float(np.mean(hit / k if k > 0 else np.zeros_like(hit)) * 100)
+    found = float(np.mean((c > 0).astype(np.float64)))
+    return {"num_queries": int(c.size), "recall": recall, "precision": precision, "mrr": found, "map": found}
+
+
+def evaluate_threshold_retrieval(query_emb, index, threshold: float = 0.7, k_values: Sequence[int] = (1, 5, 10),
+                                 return_sets: bool = False, device=None):
+    """scripts/evaluate.py's evaluate_epoch on embeddings: every row of `index` (a CosineIndex, or
+    [N, d] embeddings to build one from) with cosine >= threshold is relevant to a query; metrics as
+    threshold_metrics, plus "threshold". The relevant sets come from CosineIndex.search_above -- the
+    lengths are all the metrics need (the relevant set is a prefix of the ranking), and no [nq, N]
+    matrix or per-query argsort exists. return_sets: also (offsets, scores, ids) on the CPU, the
+    relevant rows of each query, best first."""
+    own = not isinstance(index, CosineIndex)
+    if own:
+        rows = torch.as_tensor(index)
+        if rows.dim() != 2:
+            raise ValueError(f"index embeddings [N, d] expected, got {tuple(rows.shape)}")
+        idx = CosineIndex(rows.shape[1], capacity=max(rows.shape[0], 1), device=device)
+    else:
+        idx = index
+    try:
+        if own:
+            idx.append(rows)
+        off, s, i = idx.search_above(query_emb, float(threshold))
+        off = off.cpu()
+        m = threshold_metrics(off[1:] - off[:-1], len(idx), k_values)
+        m["threshold"] = float(threshold)
+        return (m, (off, s.cpu(), i.cpu())) if return_sets else m
+    finally:
+        if own:
+            idx.close()
+
+
 # ------------------------------------------------------------------ contrastive loss --
 def loss_from_lse(lse_i2t, lse_t2i, pair_scores, temperature: float, err_i2t=None, err_t2i=None) -> Dict[str, float]:
     """The symmetric InfoNCE loss of train_lora.py:83-108 from its row reductions, in fp64:
@@ -297,6 +355,15 @@ class CLIPEvaluator:
             raise ValueError("No valid samples found! Check image paths.")
         return evaluate_retrieval(img, txt, k_values)
 
+    def evaluate_threshold_retrieval(self, test_csv, image_root_dir, threshold: float = 0.7,
+                                     k_values: Sequence[int] = (1, 5, 10)) -> Dict:
+        """The threshold evaluator (scripts/evaluate.py) on the CSV's pairs: the captions are the
+        queries, the images the index -- every image at or above the cosine is relevant."""
+        img, txt = self.encode_pairs(test_csv, image_root_dir)
+        if img.numel() == 0:
+            raise ValueError("No valid samples found! Check image paths.")
+        return evaluate_threshold_retrieval(txt, img, threshold, k_values)
+
     def evaluate_loss(self, test_csv, image_root_dir, temperature: float = 0.07, batch_size=None) -> Dict[str, float]:
         """contrastive_loss of the CSV's pairs (train_lora.py's validation loss on this adapter)"""
         img, txt = self.encode_pairs(test_csv, image_root_dir)
@@ -312,4 +379,4 @@ class CLIPEvaluator:
 
 
 __all__ = ["retrieval_ranks", "recall_at_k", "mrr", "mean_average_precision", "evaluate_retrieval",
-           "matching_accuracy", "contrastive_loss", "loss_from_lse", "batched_loss", "read_pairs", "CLIPEvaluator"]
+           "matching_accuracy", "threshold_metrics", "evaluate_threshold_retrieval", "contrastive_loss", "loss_from_lse", "batched_loss", "read_pairs", "CLIPEvaluator"]

@@ -161,6 +161,39 @@ class FinderIndex:
         return {"id": id, "image_path": self.index.image_paths[id] if id < len(self.index.image_paths) else "",
                 "description": stored, "location": location}
 
+    def similar_items(self, descriptions: Sequence, threshold: float,
+                      locations: Optional[Sequence[Optional[str]]] = None) -> List[List[Dict]]:
+        """Which existing reports describe the same thing: for each description (encoded as
+        report_items encodes it) every item of the index whose cosine is >= threshold, best first,
+        as {"id", "score", "image_path", "description"}. Nothing in the index changes."""
+        n = len(descriptions)
+        locations = list(locations) if locations is not None else [None] * n
+        is_str = [isinstance(d, str) for d in descriptions]
+        if any(is_str) and not all(is_str):
+            raise ValueError("descriptions must be all strings or all token-id lists, not a mix")
+        if not all(is_str) and any(loc for loc in locations):
+            raise ValueError("a location needs a string description (token ids cannot carry it)")
+        idx = self.index
+        if n == 0:
+            return []
+        if idx.num_items == 0:
+            return [[] for _ in range(n)]
+        texts = [_full_text(d, loc) if isinstance(d, str) else d for d, loc in zip(descriptions, locations)]
+        if all(isinstance(t, str) for t in texts) or n == 1:
+            ids = self.processor.token_ids(texts if n > 1 or isinstance(texts[0], str) else texts[0])
+        else:
+            ids = self.processor.token_ids(texts)
+        emb = self.model.encode_ids(ids.to(self.model.device), normalize=True).to(torch.float32)
+        off, scores, rows = idx._gpu.search_above(emb, float(threshold))
+        off, scores, rows = off.tolist(), scores.tolist(), rows.tolist()
+        out = []
+        for q in range(n):
+            out.append([{"id": r, "score": float(s),
+                         "image_path": idx.image_paths[r] if 0 <= r < len(idx.image_paths) else "",
+                         "description": idx.texts[r] if 0 <= r < len(idx.texts) else ""}
+                        for r, s in zip(rows[off[q]: off[q + 1]], scores[off[q]: off[q + 1]])])
+        return out
+
     def flush(self) -> None:
         """Write the index in the reference .pt format (finder_service.py:93-103)."""
         self.index.save(self.index_path)

@@ -68,6 +68,7 @@ class CosineIndex:
         C.check(C.lib().clm_index_create(self.device.index, max(int(capacity), 1), self.dim_p, ctypes.byref(h)),
                 "clm_index_create")
         self._h = h
+        self._offset = 0
 
     def __len__(self) -> int:
         return int(C.lib().clm_index_size(self._h))
@@ -121,6 +122,7 @@ class CosineIndex:
 
     def set_offset(self, offset: int) -> None:
         C.check(C.lib().clm_index_set_offset(self._h, int(offset)))
+        self._offset = int(offset)
 
     def read(self, start: int = 0, n: Optional[int] = None) -> torch.Tensor:
         n = len(self) - start if n is None else n
@@ -200,6 +202,81 @@ class CosineIndex:
         v = (ctypes.c_int64 * 11)()
         C.check(C.lib().clm_index_stats2(self._h, v, 11))
         return {"band": v[7], "exact": v[8], "overflow": v[9], "band_rows": v[10]}
+
+    # ------------------------------------------------------- threshold search --
+    def _thresholds(self, threshold, nq: int) -> torch.Tensor:
+        t = torch.as_tensor(threshold, dtype=torch.float32).reshape(-1)
+        if t.numel() == 1 and nq != 1:
+            t = t.expand(nq)
+        if t.numel() != nq:
+            raise ValueError(f"threshold must be a float or hold one value per query ({nq}), got {t.numel()}")
+        return t.to(self.device).contiguous()
+
+    def _held_result(self, off: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        total = int(off[-1])
+        s = torch.empty((total,), dtype=torch.float32, device=self.device)
+        i = torch.empty((total,), dtype=torch.int64, device=self.device)
+        if total:
+            C.check(C.lib().clm_index_search_above_read(self._h, 0, total, C.ptr(s), C.ptr(i),
+                                                        C.stream_of(self.device)), "clm_index_search_above_read")
+        return off.to(self.device), s, i
+
+    def search_above(self, queries, threshold, band_cap: int = 0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """Every row at or above a cosine, exactly: (offsets [nq + 1] i64, scores [total] f32, ids
+        [total] i64) on the GPU. Query i owns entries [offsets[i], offsets[i + 1]): the rows whose
+        exact score (that of `search`) is >= threshold[i] or NaN, in the search order (score desc, id
+        asc) -- as many as count_above(q, threshold, INT64_MAX) says, and bit for bit the first
+        entries of search(q, k) for any k that holds them. threshold: a float or one value per query
+        (-inf: every row; a NaN threshold: only NaN-scoring rows). No [nq, N] matrix; a low
+        threshold returns up to nq x N entries, each re-scored exactly (clm_index_search_above).
+        band_cap: as in `rank`. ValueError for an empty index."""
+        q = self._queries(queries)
+        nq = q.shape[0]
+        t = self._thresholds(threshold, nq)
+        off = torch.empty((nq + 1,), dtype=torch.int64)
+        code = C.CLM_F32 if q.dtype == torch.float32 else C.CLM_F16
+        C.check(C.lib().clm_index_search_above(self._h, C.ptr(q) if nq else None, code, nq, C.ptr(t) if nq else None,
+                                               C.ptr(off), int(band_cap), C.stream_of(self.device)),
+                "clm_index_search_above")
+        return self._held_result(off)
+
+    def search_above_rows(self, start: int, n: int, threshold, band_cap: int = 0):
+        """search_above with the index's own rows [start, start + n) (global ids) as the queries,
+        taken where they lie in HBM (clm_index_search_above_rows)."""
+        n = int(n)
+        t = self._thresholds(threshold, n)
+        off = torch.empty((n + 1,), dtype=torch.int64)
+        C.check(C.lib().clm_index_search_above_rows(self._h, int(start), n, C.ptr(t) if n else None, C.ptr(off),
+                                                    int(band_cap), C.stream_of(self.device)),
+                "clm_index_search_above_rows")
+        return self._held_result(off)
+
+    def range_stats(self) -> dict:
+        """search_above queries served by the MFMA filter pass (`fast`), by the exact route (`exact`),
+        and those whose candidate list overflowed its capacity (`overflow`)"""
+        v = (ctypes.c_int64 * 17)()
+        C.check(C.lib().clm_index_stats2(self._h, v, 17))
+        return {"fast": v[14], "exact": v[15], "overflow": v[16]}
+
+    def near_duplicates(self, threshold: float, block: int = 4096):
+        """The self-join under a threshold: (pairs [P, 2] i64, scores [P] f32) on the GPU, every
+        unordered pair of rows i < j (global ids) whose exact
+        cosine is >= threshold, once, without the self match, ordered by (i asc, score desc, j asc).
+        search_above_rows over row blocks of `block`: the memory is that of one block's result."""
+        n, offset = len(self), getattr(self, "_offset", 0)
+        pairs, scores = [], []
+        for r0 in range(0, n, max(int(block), 1)):
+            m = min(int(block), n - r0)
+            off, s, j = self.search_above_rows(int(offset) + r0, m, float(threshold))
+            i = torch.repeat_interleave(torch.arange(int(offset) + r0, int(offset) + r0 + m, device=self.device),
+                                        off[1:] - off[:-1])
+            keep = j > i   # the result is already (i asc, score desc, j asc); a mask keeps that order
+            pairs.append(torch.stack([i[keep], j[keep]], 1))
+            scores.append(s[keep])
+        if not pairs:
+            return (torch.empty((0, 2), dtype=torch.int64, device=self.device),
+                    torch.empty((0,), dtype=torch.float32, device=self.device))
+        return torch.cat(pairs, 0), torch.cat(scores, 0)
 
     # ------------------------------------------------------------ log-sum-exp --
     def logsumexp(self, queries, scale: float, head: int = 64, band_cap: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -504,6 +581,34 @@ class TextSearchIndex:
     def search_by_image(self, image_path, model, processor, device, top_k: int = 5) -> List[SearchResult]:
         from .clip_model import encode_image
         return self.search_with_embedding(encode_image(image_path, model, processor, device), top_k=top_k)
+
+    def search_above_with_embedding(self, query_emb: torch.Tensor, threshold: float) -> List[SearchResult]:
+        """Every item whose cosine with the query is >= threshold (CosineIndex.search_above), best
+        first; query_emb: shape (d,) or (1, d), metadata looked up as search_with_embedding does."""
+        query_emb = torch.as_tensor(query_emb)
+        if query_emb.ndim == 1:
+            query_emb = query_emb.unsqueeze(0)
+        elif query_emb.ndim != 2 or query_emb.shape[0] != 1:
+            raise ValueError(f"query_emb must be shape (d,) or (1, d), got {tuple(query_emb.shape)}")
+        if query_emb.shape[-1] != self.dim:
+            raise ValueError(f"query_emb dim {query_emb.shape[-1]} != index dim {self.dim}")
+        if self.num_items == 0:
+            return []
+        _, scores, indices = self._gpu.search_above(query_emb, float(threshold))
+        results: List[SearchResult] = []
+        for idx, score in zip(indices.tolist(), scores.tolist()):
+            img = self.image_paths[idx] if 0 <= idx < len(self.image_paths) else ""
+            txt = self.texts[idx] if 0 <= idx < len(self.texts) else ""
+            results.append(SearchResult(index=idx, score=float(score), image_path=img, text=txt))
+        return results
+
+    def search_above_by_text(self, query, model, processor, device, threshold: float) -> List[SearchResult]:
+        from .clip_model import encode_text
+        return self.search_above_with_embedding(encode_text(query, model, processor, device), threshold)
+
+    def search_above_by_image(self, image_path, model, processor, device, threshold: float) -> List[SearchResult]:
+        from .clip_model import encode_image
+        return self.search_above_with_embedding(encode_image(image_path, model, processor, device), threshold)
 
     # ------------------------------------------------------- resident append --
     def append(self, embeddings, image_paths: Sequence[str] = (), texts: Sequence[str] = ()) -> None:

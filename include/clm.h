@@ -29,6 +29,9 @@
  *                              normaliser of softmax match probabilities, without a [nq, N] matrix
  *   clm_index_lse64            (new) the same reduction and the pair scores on unrounded fp64
  *                              cosines: that function on float64 tensors
+ *   clm_index_search_above     (new) every index row at or above a cosine, exactly: the relevant set
+ *                              of scripts/evaluate.py:141-269 (evaluate_single_query: cosine >= 0.7),
+ *                              "which reports describe the same item", near-duplicate listing
  *   clm_cosine_scores          cosine_similarity similarity.py:10-33
  *   clm_topk_merge             (new) merge of per-shard top-k lists for the
  *                              8-GPU sharded search
@@ -288,12 +291,51 @@ int clm_index_lse(clm_index* idx, const void* q, int q_dtype, int64_t nq, double
 int clm_index_lse64(clm_index* idx, const void* q, int q_dtype, int64_t nq, double scale, const int64_t* target,
                     double* out_lse, double* out_pair, void* stream);
 
+/* Threshold search: WHICH rows score at or above a threshold. With s_j the exact score of row j (as
+ * clm_index_search returns it) and tau = threshold[i] (one fp32 per query), the result of query i is
+ *
+ *     { j : s_j >= tau, or s_j is NaN }        (rank_ahead(s_j, id_j, tau, INT64_MAX) of the rank order)
+ *
+ * ordered (score desc, global id asc), NaN above every number. So its length is
+ * clm_index_count_above(q_i, tau, INT64_MAX), it equals bit for bit the first entries of
+ * clm_index_search(q_i, k) for every k that holds it, and the results of row shards concatenate and
+ * merge to the whole index's. tau = -inf returns every row, +inf (or 2.0) none but NaN-scoring rows, a
+ * NaN tau only the NaN-scoring rows. NaN scores lead a result, in id order, and are returned with
+ * their sign bit cleared (the sort key of a score is its bit pattern). Two calls return the same bits (integer atomics only; a sort
+ * makes the order canonical).
+ * Results are ragged, so the index holds them: out_offsets [nq + 1] (host or device) says that query
+ * i owns entries [offsets[i], offsets[i + 1]) of the held result, clm_index_search_above_read copies
+ * entries [start, start + n) -- exact scores f32, global ids i64, host or device -- until the next
+ * threshold search, clm_index_reset, a mutation (append / import / remove / update) or destroy.
+ * clm_index_search_above_rows takes the index's own rows [row0, row0 + nrows) as the queries (row0 a
+ * global id; the fp32 rows where the index keeps them, else its fp16 rows) without moving them: the
+ * self-join behind near-duplicate listing.
+ * Fast route: one fp16 MFMA pass lists per query the rows whose fp16-pass score reaches tau minus the
+ * rank margin, they are re-scored exactly, the rows that pass are sorted. Exact route: windows of
+ * exact scores, counted, then collected. band_cap: as in clm_index_rank (list capacity per query in
+ * the CLM_RANK_CAP_MASK bits, 0 = default; a list that overflows is redone with the capacity it
+ * needs, then by the exact route); CLM_RANK_EXACT / CLM_RANK_BAND force a route. The whole call is
+ * exact under clm_index_rank's conditions (a zero or non-finite row norm in the index, dim > 8192,
+ * size > 2^31 - 1, nq x size <= 2^24, $CLM_SEARCH_FULL=1); a single query is when its tau or its norm
+ * is not finite. Nothing is sized by nq x size; a low tau returns up to nq x size entries (12 B each,
+ * 28 B while they are sorted), each re-scored exactly. At most 2^32 - 1 rows per index.
+ * CLM_E_ARG: an empty index, a null pointer, a dtype other than f32 / f16, nq < 0, rows outside the
+ * index. CLM_E_OOM: the result cannot be allocated (clm_last_error names the entry count); the index's
+ * rows are untouched. clm_index_search_above_read: CLM_E_STATE when no result is held, when it was
+ * invalidated, or when the range is outside it. */
+int clm_index_search_above(clm_index* idx, const void* q, int q_dtype, int64_t nq, const float* threshold,
+                           int64_t* out_offsets, int band_cap, void* stream);
+int clm_index_search_above_rows(clm_index* idx, int64_t row0, int64_t nrows, const float* threshold,
+                                int64_t* out_offsets, int band_cap, void* stream);
+int clm_index_search_above_read(clm_index* idx, int64_t start, int64_t n, float* out_scores, int64_t* out_idx,
+                                void* stream);
+
 /* search-path counters since creation: queries served by the sampled single-pass bounded
  * search (`filtered`), by the exact scan or the fp16-scan-bounded search (`exact`), and
  * bounded queries whose candidate list overflowed (redone by a whole-list pass, or by the exact
  * scan when the list is longer than 8192 / k chunks of 4096) */
 int clm_index_stats(const clm_index* idx, int64_t* filtered, int64_t* exact, int64_t* overflow);
-/* out[0..n), n <= 14: sampled bounded, fp16-scan bounded, full exact scan, overflow re-runs, then the
+/* out[0..n), n <= 17: sampled bounded, fp16-scan bounded, full exact scan, overflow re-runs, then the
  * sampled queries whose filter pass ran on the G2 256 x 192 tiles / on gemm_kernel 256 x 256 (chosen
  * per query block from the block's sampled candidate counts: near-duplicate blocks take the latter),
  * then the queries served by the small-batch streaming search (nq <= 16 on a large index: one pass
@@ -301,7 +343,8 @@ int clm_index_stats(const clm_index* idx, int64_t* filtered, int64_t* exact, int
  * served by the band pass, by the exact route, those of the latter whose band list overflowed, and
  * the band rows re-scored for the band-served queries, then the clm_index_lse queries served by the
  * fast route, by the exact route (clm_index_lse64's among them), and those whose band list overflowed
- * its capacity */
+ * its capacity, then the threshold-search queries served by the MFMA pass, by the exact route, and
+ * those whose candidate list overflowed its capacity */
 int clm_index_stats2(const clm_index* idx, int64_t* out, int n);
 
 /* full cosine matrix, exact: out [nq, n] f32 = fp32(cos64(q_i, c_j)), any dim */
