@@ -24,6 +24,7 @@ CLM_PAIR_GRAPH = 1
 CLM_PAIR_SPLIT_SHIFT = 8
 CLM_RANK_EXACT, CLM_RANK_BAND, CLM_RANK_CAP_MASK = 1 << 30, 1 << 29, (1 << 29) - 1   # band_cap flag bits (clm.h)
 CLM_LSE_EXACT, CLM_LSE_FAST = CLM_RANK_EXACT, CLM_RANK_BAND
+CLM_MASK_EXACT, CLM_MASK_PASS, CLM_MASK_GATHER = 1 << 30, 1 << 29, 1 << 28   # clm_index_search_masked route flags
 
 
 class TowerDesc(ctypes.Structure):
@@ -85,6 +86,8 @@ def lib():
         "clm_index_update": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int64, c_void_p]),
         "clm_index_read": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
         "clm_index_search": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
+        "clm_index_search_masked": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p,
+                                            c_void_p]),
         "clm_index_count_above": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_int,
                                           c_void_p]),
         "clm_index_rank": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
@@ -174,6 +177,7 @@ EXPORTED = (
     "clm_text_plan", "clm_gemm_attn",
     "clm_layernorm_ex", "clm_gemm_ex", "clm_patchify", "clm_write_cls", "clm_gather_pooled", "clm_pool_project",
     "clm_index_search_above", "clm_index_search_above_rows", "clm_index_search_above_read",
+    "clm_index_search_masked",
 )
 CLM_EPI_STORE, CLM_EPI_GELU, CLM_EPI_RESID, CLM_EPI_SCORE = 0, 1, 2, 4
 CLM_EPI_PATCH = 3   # clm_gemm_ex only

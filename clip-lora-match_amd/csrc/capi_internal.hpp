@@ -71,6 +71,10 @@ struct Layout {
 }  // namespace capi
 }  // namespace clm
 
+// Every device buffer below is owned by the index and released by clm_index_destroy. The filtered
+// search's gather route (capi_search.cpp masked_gather) builds a temporary clm_index on the stack
+// around gathered rows, lends it ws2 / ws3 / ws4 and frees every other lazily allocated buffer when
+// it returns: a new device buffer added here must be added to both lists.
 struct clm_index {
   int dev = 0;
   int64_t cap = 0, n = 0, dim = 0, offset = 0;
@@ -104,7 +108,9 @@ struct clm_index {
   // whose EPI_LSE band list overflowed its capacity
   // [14] / [15]: threshold-search queries served by the EPI_FILTER pass / by the exact route, [16]:
   // those whose candidate list overflowed its capacity
-  int64_t search_stats[17] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  // [17] / [18] / [19]: masked-search queries served by the pass route / the gather route / the exact
+  // route (a pass-route query redone exactly counts in [19])
+  int64_t search_stats[20] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   // The held result of the last threshold search (clm_index_search_above / _rows): res_n entries
   // (exact score, global id) in CSR order, read by clm_index_search_above_read until the next
   // threshold search, reset, mutation or destroy (res_valid). rg_comp / rg_comp2: the composites it

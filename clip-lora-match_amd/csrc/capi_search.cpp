@@ -178,8 +178,11 @@ constexpr int CAND_CAP = 2048;
 
 // Chunked scan: score chunks [nqb, ch] -- fp16 MFMA (EPI_SCORE GEMM) or exact fp64 cosines
 // (exact_scores) -- radix top-k per chunk row, merge of the chunk lists. Any k <= 1024, any N.
+// allow (exact scan only): the prepared words of a filtered search -- every window's disallowed
+// entries become -inf before its top-k (mask_fill), so they sort behind every allowed row
 static int search_scan(clm_index* x, bool exact, const u16* q16, const float* qinv, const float* q32,
-                       const double* qn, int64_t nq, int k, float* osc, int64_t* oix, hipStream_t st) {
+                       const double* qn, int64_t nq, int k, float* osc, int64_t* oix, hipStream_t st,
+                       const uint32_t* allow = nullptr) {
   const int dim = (int)x->dim;
   const int64_t N = x->n;
   const size_t budget = (size_t)512 << 20;
@@ -213,6 +216,7 @@ static int search_scan(clm_index* x, bool exact, const u16* q16, const float* qi
       if (exact) {
         const ExactRows er = exact_rows(x, r0);
         KCHK(exact_scores(q32 + q0 * dim, qn + q0, nb, er.p, er.f16, rn, dim, sc, ch, st));
+        if (allow) KCHK(mask_fill(sc, ch, nb, rn, r0, allow, st));
       } else {
         GemmArgs ga{};
         ga.A = q16 + q0 * dim; ga.lda = dim; ga.W = x->rows + r0 * dim; ga.ldw = dim;
@@ -679,27 +683,16 @@ static int search_small(clm_index* x, const u16* q16, const float* qinv, const f
 //  * small problems (nq * N <= 2^24 dot products, or $CLM_SEARCH_FULL=1): the exact scan;
 //  * otherwise (or $CLM_SEARCH_BOUNDED=1) search_bounded, sampled when the index is large
 //    enough for sampling to pay ($CLM_SEARCH_EXACT=1 forces the chunked fp16 scan for step 1).
-int clm_index_search(clm_index* x, const void* q, int q_dtype, int64_t nq, int k, float* out_scores,
-                     int64_t* out_idx, void* stream) {
-  if (!x || nq < 0 || (nq > 0 && (!q || !out_scores || !out_idx))) return fail(CLM_E_ARG, "bad argument");
-  if (q_dtype != CLM_F32 && q_dtype != CLM_F16) return fail(CLM_E_ARG, "queries must be f32 or f16");
-  if (k < 1) return fail(CLM_E_ARG, "k must be >= 1");
-  if (k > (1 << 26)) return fail(CLM_E_ARG, "k must be <= 2^26");
-  if (nq == 0) return CLM_OK;
-  DeviceGuard g(x->dev);
-  hipStream_t st = (hipStream_t)stream;
+// (search_route: the routes, for queries already staged -- clm_index_search's, and the filtered
+// search's gather route on its temporary index)
+// small_max: up to this many dot products the exact scan serves the call (the gather route passes a
+// lower bound for its temporary index)
+constexpr double SMALL_PROBLEM = (double)(1 << 24);
+static int search_route(clm_index* x, const QueryStage& qs, int64_t nq, int k, float* osc, int64_t* oix,
+                        hipStream_t st, double small_max = SMALL_PROBLEM) {
   const int dim = (int)x->dim;
   const int64_t N = x->n;
-  const bool o_dev = is_device_ptr(out_scores) && is_device_ptr(out_idx);
-  Layout lay;   // the results' staging, when they go to the host
-  const size_t o_os = o_dev ? 0 : lay.take((size_t)nq * k * 4);
-  const size_t o_oi = o_dev ? 0 : lay.take((size_t)nq * k * 8);
-  QueryStage qs;
-  int r = stage_queries(x, q, q_dtype, nq, lay.total(), st, &qs);
-  if (!r) r = stage_queries_f16(x, qs, nq, st);
-  if (r) return r;
-  float* osc = o_dev ? out_scores : (float*)(qs.extra + o_os);
-  int64_t* oix = o_dev ? out_idx : (int64_t*)(qs.extra + o_oi);
+  int r;
   const char* e_full = getenv("CLM_SEARCH_FULL");
   const char* e_exact = getenv("CLM_SEARCH_EXACT");
   const char* e_bounded = getenv("CLM_SEARCH_BOUNDED");   // tests: bounded search at any size
@@ -718,7 +711,7 @@ int clm_index_search(clm_index* x, const void* q, int q_dtype, int64_t nq, int k
     r = search_scan_large(x, qs.q32, qs.qn, nq, k, osc, oix, st);
     x->search_stats[1] += nq;
   } else if ((e_full && atoi(e_full)) || N == 0 || dim > MARGIN_MAX_DIM ||
-             (!force_bounded && (double)nq * (double)N <= (double)(1 << 24))) {
+             (!force_bounded && (double)nq * (double)N <= small_max)) {
     r = search_scan(x, true, qs.q16, qs.qinv, qs.q32, qs.qn, nq, k, osc, oix, st);
     x->search_stats[1] += nq;
   } else {
@@ -729,10 +722,305 @@ int clm_index_search(clm_index* x, const void* q, int q_dtype, int64_t nq, int k
     const bool sampled = !(e_exact && atoi(e_exact)) && k <= 256 && N >= 4 * S && S <= (1 << 18);
     r = search_bounded(x, sampled, S, qs.q16, qs.qinv, qs.q32, qs.qn, nq, k, osc, oix, st);
   }
+  return r;
+}
+
+int clm_index_search(clm_index* x, const void* q, int q_dtype, int64_t nq, int k, float* out_scores,
+                     int64_t* out_idx, void* stream) {
+  if (!x || nq < 0 || (nq > 0 && (!q || !out_scores || !out_idx))) return fail(CLM_E_ARG, "bad argument");
+  if (q_dtype != CLM_F32 && q_dtype != CLM_F16) return fail(CLM_E_ARG, "queries must be f32 or f16");
+  if (k < 1) return fail(CLM_E_ARG, "k must be >= 1");
+  if (k > (1 << 26)) return fail(CLM_E_ARG, "k must be <= 2^26");
+  if (nq == 0) return CLM_OK;
+  DeviceGuard g(x->dev);
+  hipStream_t st = (hipStream_t)stream;
+  const bool o_dev = is_device_ptr(out_scores) && is_device_ptr(out_idx);
+  Layout lay;   // the results' staging, when they go to the host
+  const size_t o_os = o_dev ? 0 : lay.take((size_t)nq * k * 4);
+  const size_t o_oi = o_dev ? 0 : lay.take((size_t)nq * k * 8);
+  QueryStage qs;
+  int r = stage_queries(x, q, q_dtype, nq, lay.total(), st, &qs);
+  if (!r) r = stage_queries_f16(x, qs, nq, st);
+  if (r) return r;
+  float* osc = o_dev ? out_scores : (float*)(qs.extra + o_os);
+  int64_t* oix = o_dev ? out_idx : (int64_t*)(qs.extra + o_oi);
+  r = search_route(x, qs, nq, k, osc, oix, st);
   if (r) return r;
   if (!o_dev) {
     HIPCHK(hipMemcpyAsync(out_scores, osc, (size_t)nq * k * 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(out_idx, oix, (size_t)nq * k * 8, hipMemcpyDeviceToHost, st));
+  }
+  HIPCHK(hipStreamSynchronize(st));   // workspaces are reused by the next call
+  return CLM_OK;
+}
+
+// ---- filtered search (clm_index_search_masked) ----------------------------------------------
+// The first k of the ALLOWED rows in the search order. Three routes, the same bits on each (every
+// score comes from the exact_cos.hpp routine, every order from (exact score desc, local row asc)):
+//  A exact:  search_scan(exact) with every window's disallowed entries set to -inf (mask_fill);
+//  B gather: the allowed rows gathered in order into a temporary index of clm_index_import's form,
+//            searched by search_route, positions mapped back through the list (monotone: ties keep
+//            their order);
+//  C pass:   theta from a sample of the ALLOWED rows (a subset of them: its fp16-pass k-th best is
+//            never above theirs), one EPI_FILTER_MASK pass, rescore_select; a query whose
+//            list overflowed CAND_CAP or ended short of min(k, P) is redone by route A.
+// -inf marks a dead entry everywhere (an exact cosine is finite or NaN); map_ids turns it into -1.
+
+// device buffers of one call, released when it returns (the call keeps no state)
+struct CallBufs {
+  hipStream_t st;
+  std::vector<void*> p;
+  explicit CallBufs(hipStream_t s) : st(s) {}
+  void* take(size_t bytes) {
+    void* d = nullptr;
+    if (hipMalloc(&d, std::max<size_t>(bytes, 256)) != hipSuccess) {
+      (void)hipGetLastError();
+      return nullptr;
+    }
+    p.push_back(d);
+    return d;
+  }
+  ~CallBufs() {
+    if (p.empty()) return;
+    (void)hipStreamSynchronize(st);
+    for (void* d : p) (void)hipFree(d);
+  }
+};
+
+// the gather route switches in at P * MASK_GATHER_DIV <= N (the pass route streams all N rows, the
+// gather route moves and searches P of them). Measured at 1 M x 512, 4,096 queries, k = 5
+// (profiles/masked_search_ab.txt): at P = N / 2 gather 6.2 / 4.3 ms (random / contiguous mask) against
+// pass 6.4 / 5.4, at N / 8 2.2 / 1.7 against 5.6 / 4.6; at P = N pass 6.4 against gather 7.7
+constexpr int64_t MASK_GATHER_DIV = 2;
+// ... and for small batches (nq <= 16, the unmasked search's small-batch bound) at P * 8 <= N: one
+// query pays the gather of P rows alone. 1 M rows: pass 0.38 / 0.36 ms at N / 2 and N / 8 against gather
+// 0.72 / 0.58; 10 M rows: pass 2.35 / 2.30 against gather 3.88 / 1.64, and 0.46 at 1 %
+constexpr int64_t MASK_GATHER_DIV_SMALL = 8;
+// the temporary index of the gather route takes the exact scan up to this many dot products only
+// (with the unmasked search's 2^24, 4,096 queries x 1,000 gathered rows took the fp64 scan: 10.1 ms,
+// profiles/masked_search_ab.txt)
+constexpr double MASK_GATHER_SMALL = (double)(1 << 20);
+
+static int masked_exact(clm_index* x, const QueryStage& qs, int64_t nq, int k, const uint32_t* words, float* osc,
+                        int64_t* oix, hipStream_t st) {
+  int r = search_scan(x, true, nullptr, nullptr, qs.q32, qs.qn, nq, k, osc, oix, st, words);
+  if (r) return r;
+  KCHK(map_ids(osc, oix, nq * k, nullptr, 0, st));
+  return CLM_OK;
+}
+
+// queries `redo` of the batch served again by route A, their rows of osc / oix replaced
+static int masked_redo(clm_index* x, const QueryStage& qs, int k, const uint32_t* words,
+                       const std::vector<int64_t>& redo, float* osc, int64_t* oix, hipStream_t st) {
+  return redo_subset(x, redo, {{qs.q32, x->dim * 4}, {qs.qn, 8}}, {{osc, (int64_t)k * 4}, {oix, (int64_t)k * 8}},
+                     "masked redo", st, [&](void* const* in, void* const* out) -> int {
+                       int r = search_scan(x, true, nullptr, nullptr, (const float*)in[0], (const double*)in[1],
+                                           (int64_t)redo.size(), k, (float*)out[0], (int64_t*)out[1], st, words);
+                       if (r) return r;
+                       KCHK(map_ids((const float*)out[0], (int64_t*)out[1], (int64_t)redo.size() * k, nullptr, 0, st));
+                       return CLM_OK;
+                     });
+}
+
+static int masked_gather(clm_index* x, const QueryStage& qs, int64_t nq, int k, const uint32_t* words,
+                         const uint32_t* list, int64_t P, float* osc, int64_t* oix, int64_t* n_redo,
+                         hipStream_t st) {
+  const int dim = (int)x->dim;
+  CallBufs bufs(st);
+  u16* t16 = (u16*)bufs.take((size_t)P * dim * 2);
+  float* tinv = t16 ? (float*)bufs.take((size_t)P * 4) : nullptr;
+  float* t32 = tinv && x->rows32 ? (float*)bufs.take((size_t)P * dim * 4) : nullptr;
+  if (!t16 || !tinv || (x->rows32 && !t32))
+    return fail(CLM_E_OOM, "masked search: the temporary index of " + std::to_string(P) + " rows cannot be allocated");
+  KCHK(mask_gather(x->rows, x->rows32, x->inv, dim, list, P, P, t16, t32, tinv, st));
+  // the temporary index: the gathered rows, offset 0 (ids = list positions), the parent's block
+  // workspaces on loan (the staged queries live in x->ws, which no route touches)
+  clm_index tmp;
+  tmp.dev = x->dev; tmp.cap = P; tmp.n = P; tmp.dim = x->dim; tmp.offset = 0;
+  tmp.rows = t16; tmp.inv = tinv; tmp.rows32 = t32;
+  tmp.ws2 = x->ws2; tmp.ws2_bytes = x->ws2_bytes; tmp.ws3 = x->ws3; tmp.ws3_bytes = x->ws3_bytes;
+  tmp.ws4 = x->ws4; tmp.ws4_bytes = x->ws4_bytes;
+  int r = search_route(&tmp, qs, nq, k, osc, oix, st, MASK_GATHER_SMALL);
+  x->ws2 = tmp.ws2; x->ws2_bytes = tmp.ws2_bytes; x->ws3 = tmp.ws3; x->ws3_bytes = tmp.ws3_bytes;
+  x->ws4 = tmp.ws4; x->ws4_bytes = tmp.ws4_bytes;
+  if (!r && map_ids(osc, oix, nq * k, list, x->offset, st) != hipSuccess) r = fail(CLM_E_HIP, "map_ids launch failed");
+  // a list short of min(k, P) entries: a NaN-scoring (zero or non-finite) query, which the MFMA routes
+  // of the unmasked search leave without candidates -- route A defines its result
+  const int64_t need = std::min<int64_t>(k, P);
+  std::vector<int64_t> last(nq);
+  hipError_t e = r ? hipSuccess
+                   : hipMemcpy2DAsync(last.data(), 8, oix + (need - 1), (size_t)k * 8, 8, (size_t)nq,
+                                      hipMemcpyDeviceToHost, st);
+  (void)hipStreamSynchronize(st);
+  // everything the routes allocated lazily in the temporary index (every device buffer of clm_index
+  // that is neither the gathered rows nor on loan: see the note at the struct)
+  for (void* p : {(void*)tmp.samp, (void*)tmp.samp_inv, (void*)tmp.inv_keys, tmp.ws, tmp.mut, (void*)tmp.res_s,
+                  (void*)tmp.res_i, (void*)tmp.rg_comp, (void*)tmp.rg_comp2, tmp.rg_items})
+    if (p) (void)hipFree(p);
+  if (r) return r;
+  if (e != hipSuccess) return fail(CLM_E_HIP, std::string("masked search: ") + hipGetErrorString(e));
+  std::vector<int64_t> redo;
+  for (int64_t i = 0; i < nq && k <= 1024; ++i)
+    if (last[i] < 0) redo.push_back(i);
+  *n_redo = (int64_t)redo.size();
+  return masked_redo(x, qs, k, words, redo, osc, oix, st);
+}
+
+static int masked_pass(clm_index* x, const QueryStage& qs, int64_t nq, int k, const uint32_t* words,
+                       const uint32_t* list, int64_t P, int64_t S, float* osc, int64_t* oix, int64_t* n_redo,
+                       hipStream_t st) {
+  const int dim = (int)x->dim;
+  int r;
+  const int64_t ldS = round_up(S, 4) + 64;   // search_bounded's row padding
+  const int64_t nqb = band_query_block(nq, ldS * 4, 256);
+  Layout lay;
+  const size_t o_s16 = lay.take((size_t)S * dim * 2), o_si = lay.take((size_t)S * 4);
+  const size_t o_sc = lay.take((size_t)nqb * ldS * 4);
+  const size_t o_ts = lay.take((size_t)nqb * k * 4), o_ti = lay.take((size_t)nqb * k * 8);
+  const size_t o_th = lay.take((size_t)nq * 4), o_cnt = lay.take((size_t)nq * 4);
+  const size_t o_cs = lay.take((size_t)nqb * CAND_CAP * 4), o_ci = lay.take((size_t)nqb * CAND_CAP * 8);
+  if ((r = grow(&x->ws2, &x->ws2_bytes, lay.total()))) return r;
+  uint8_t* w = (uint8_t*)x->ws2;
+  u16* s16 = (u16*)(w + o_s16);
+  float* sinv = (float*)(w + o_si);
+  float* sc = (float*)(w + o_sc);
+  float* ts = (float*)(w + o_ts);
+  int64_t* ti = (int64_t*)(w + o_ti);
+  float* th = (float*)(w + o_th);
+  int* cnt = (int*)(w + o_cnt);
+  float* cs = (float*)(w + o_cs);
+  int64_t* ci = (int64_t*)(w + o_ci);
+  // the sample: S rows at positions floor(i * P / S) of the allowed list, in buffers of this call
+  KCHK(mask_gather(x->rows, nullptr, x->inv, dim, list, P, S, s16, nullptr, sinv, st));
+  if (S < k) KCHK(fill_f32(th, nq, -INFINITY, st));   // fewer sample rows than k: no threshold
+  for (int64_t q0 = 0; q0 < nq && S >= k; q0 += nqb) {
+    const int64_t nb = std::min(nqb, nq - q0);
+    GemmArgs ga{};
+    ga.A = qs.q16 + q0 * dim; ga.lda = dim; ga.W = s16; ga.ldw = dim;
+    ga.M = (int)nb; ga.N = (int)S; ga.K = dim; ga.out = sc; ga.ldo = ldS;
+    ga.rscale = qs.qinv + q0; ga.cscale = sinv;
+    KCHK(gemm(false, EPI_SCORE, ga, st));
+    if (k <= 8 && !g_kth_radix) {
+      KCHK(kth_thresholds(sc, ldS, nb, S, k, RESCORE_MARGIN, th + q0, st));
+    } else {
+      KCHK(topk_rows(sc, ldS, nb, S, k, 0, ts, ti, k, st));
+      KCHK(filter_thresholds(ts, k, nb, k, RESCORE_MARGIN, th + q0, st));
+    }
+  }
+  HIPCHK(hipMemsetAsync(cnt, 0, (size_t)nq * 4, st));
+  const ExactRows xr = exact_rows(x);
+  for (int64_t q0 = 0; q0 < nq; q0 += nqb) {
+    const int64_t nb = std::min(nqb, nq - q0);
+    GemmArgs gf = index_pass(x, qs.q16 + q0 * dim, qs.qinv + q0, nb, th + q0, cnt + q0, ci, CAND_CAP);
+    gf.cand_s = cs;
+    gf.cbound = inv_keys_of(x, st);
+    gf.mask = words;
+    KCHK(gemm_cfg(false, EPI_FILTER_MASK, -1, gf, st));
+    KCHK(rescore_select(cs, ci, cnt + q0, CAND_CAP, qs.q32 + q0 * dim, qs.qn + q0, dim, xr.p, xr.f16, x->offset,
+                        RESCORE_MARGIN, nb, k, osc + q0 * k, oix + q0 * k, st));
+  }
+  std::vector<int> hcnt(nq);
+  HIPCHK(hipMemcpyAsync(hcnt.data(), cnt, (size_t)nq * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  // an overflowed list, or one short of min(k, P) (NaN scores pass no threshold): route A decides
+  std::vector<int64_t> redo;
+  const int64_t need = std::min<int64_t>(k, P);
+  for (int64_t i = 0; i < nq; ++i)
+    if (hcnt[i] > CAND_CAP || hcnt[i] < need) redo.push_back(i);
+  *n_redo = (int64_t)redo.size();
+  return masked_redo(x, qs, k, words, redo, osc, oix, st);
+}
+
+static int search_masked(clm_index* x, const QueryStage& qs, int64_t nq, int k, const uint32_t* words,
+                         const uint32_t* bcnt, int64_t* boff, int flags, float* osc, int64_t* oix, hipStream_t st) {
+  const int64_t N = x->n, dim = x->dim;
+  const int64_t nblk = mask_blocks(N);
+  int r;
+  KCHK(mask_scan(bcnt, nblk, boff, st));
+  int64_t P = 0;
+  HIPCHK(hipMemcpyAsync(&P, boff + nblk, 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  if (P == 0) {   // nothing is allowed: (-inf, -1) lists (counted with the exact route)
+    x->search_stats[19] += nq;
+    KCHK(fill_f32(osc, nq * k, -INFINITY, st));
+    HIPCHK(hipMemsetAsync(oix, 0xFF, (size_t)nq * k * 8, st));
+    return CLM_OK;
+  }
+  const char* e_full = getenv("CLM_SEARCH_FULL");
+  const bool exact_ok = k <= 1024;   // search_scan's lists
+  // a zero or non-finite inverse norm: that row's scores are NaN, which the fp16 pass cannot list and
+  // which the unmasked routes (the gather route's search) do not place above every number -- the
+  // exact route does (mask_fill), so it serves such an index whenever its lists hold k
+  bool fin = false;
+  if ((r = inv_norms_finite(x, st, &fin))) return r;
+  const bool pass_ok = fin && k <= 256 && dim <= MARGIN_MAX_DIM && N <= 0x7FFFFFFF;
+  const int64_t Sd = round_up(std::max<int64_t>(8192, (int64_t)k * P / 256), 256);
+  enum { R_EXACT, R_GATHER, R_PASS } route;
+  if (((flags & CLM_MASK_EXACT) || !fin) && exact_ok) route = R_EXACT;
+  else if ((flags & CLM_MASK_PASS) && pass_ok) route = R_PASS;
+  else if (flags & CLM_MASK_GATHER) route = R_GATHER;
+  else if (exact_ok && ((e_full && atoi(e_full)) || dim > MARGIN_MAX_DIM)) route = R_EXACT;
+  else if (pass_ok && P >= 4 * Sd && Sd <= (1 << 18) && P * (nq <= 16 ? MASK_GATHER_DIV_SMALL : MASK_GATHER_DIV) > N)
+    route = R_PASS;
+  else route = R_GATHER;
+  if (route == R_EXACT) {
+    x->search_stats[19] += nq;
+    return masked_exact(x, qs, nq, k, words, osc, oix, st);
+  }
+  CallBufs bufs(st);
+  uint32_t* list = (uint32_t*)bufs.take((size_t)P * 4);
+  if (!list) return fail(CLM_E_OOM, "masked search: the list of " + std::to_string(P) + " allowed rows cannot be allocated");
+  KCHK(mask_compact(words, N, boff, list, st));
+  int64_t n_redo = 0;
+  if (route == R_GATHER) {
+    r = masked_gather(x, qs, nq, k, words, list, P, osc, oix, &n_redo, st);
+    x->search_stats[18] += nq - n_redo;
+    x->search_stats[19] += n_redo;
+    return r;
+  }
+  r = masked_pass(x, qs, nq, k, words, list, P, std::min(std::min<int64_t>(Sd, 1 << 18), P), osc, oix, &n_redo, st);
+  x->search_stats[17] += nq - n_redo;
+  x->search_stats[19] += n_redo;
+  return r;
+}
+
+int clm_index_search_masked(clm_index* x, const void* q, int q_dtype, int64_t nq, int k, const uint32_t* allow,
+                            int flags, float* out_scores, int64_t* out_idx, void* stream) {
+  if (!x || nq < 0 || (nq > 0 && (!q || !allow || !out_scores || !out_idx))) return fail(CLM_E_ARG, "bad argument");
+  if (q_dtype != CLM_F32 && q_dtype != CLM_F16) return fail(CLM_E_ARG, "queries must be f32 or f16");
+  if (k < 1) return fail(CLM_E_ARG, "k must be >= 1");
+  if (k > (1 << 26)) return fail(CLM_E_ARG, "k must be <= 2^26");
+  if (x->n == 0) return fail(CLM_E_ARG, "masked search: the index is empty");
+  if (nq == 0) return CLM_OK;
+  DeviceGuard g(x->dev);
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t N = x->n, nw = mask_words(N), nblk = mask_blocks(N);
+  const bool o_dev = is_device_ptr(out_scores) && is_device_ptr(out_idx), a_dev = is_device_ptr(allow);
+  Layout lay;   // the results' staging when they go to the host, then the mask's buffers
+  const size_t o_os = o_dev ? 0 : lay.take((size_t)nq * k * 4);
+  const size_t o_oi = o_dev ? 0 : lay.take((size_t)nq * k * 8);
+  const size_t o_src = a_dev ? 0 : lay.take((size_t)nw * 4);
+  const size_t o_words = lay.take((size_t)nw * 4), o_bcnt = lay.take((size_t)nblk * 4),
+               o_boff = lay.take((size_t)(nblk + 1) * 8);
+  QueryStage qs;
+  int r = stage_queries(x, q, q_dtype, nq, lay.total(), st, &qs);
+  if (!r) r = stage_queries_f16(x, qs, nq, st);
+  if (r) return r;
+  float* osc = o_dev ? out_scores : (float*)(qs.extra + o_os);
+  int64_t* oix = o_dev ? out_idx : (int64_t*)(qs.extra + o_oi);
+  const uint32_t* src = allow;
+  if (!a_dev) {
+    HIPCHK(copy_in(qs.extra + o_src, allow, (size_t)nw * 4, st));
+    src = (const uint32_t*)(qs.extra + o_src);
+  }
+  uint32_t* words = (uint32_t*)(qs.extra + o_words);
+  uint32_t* bcnt = (uint32_t*)(qs.extra + o_bcnt);
+  KCHK(mask_prepare(src, N, words, bcnt, st));
+  r = search_masked(x, qs, nq, k, words, bcnt, (int64_t*)(qs.extra + o_boff), flags, osc, oix, st);
+  if (r) return r;
+  if (!o_dev) {
+    HIPCHK(copy_out(out_scores, osc, (size_t)nq * k * 4, st));
+    HIPCHK(copy_out(out_idx, oix, (size_t)nq * k * 8, st));
   }
   HIPCHK(hipStreamSynchronize(st));   // workspaces are reused by the next call
   return CLM_OK;

@@ -63,7 +63,7 @@ __device__ __forceinline__ void epilogue_scalar(const GemmArgs& g, const f32x4 (
   for (int mb = 0; mb < TM; ++mb) {
     const int m = wrow + mb * 16;
     if (m >= g.M) continue;
-    const float rs = (EPI == EPI_SCORE || EPI == EPI_FILTER || EPI == EPI_RANK || EPI == EPI_LSE) && g.rscale ? g.rscale[m] : 1.f;
+    const float rs = (EPI == EPI_SCORE || EPI == EPI_FILTER || EPI == EPI_RANK || EPI == EPI_LSE || EPI == EPI_FILTER_MASK) && g.rscale ? g.rscale[m] : 1.f;
     float lse_sum = 0.f;   // EPI_LSE: this lane's tail terms of row m
     int64_t prow = m;
     const float* aux = nullptr;
@@ -108,6 +108,17 @@ __device__ __forceinline__ void epilogue_scalar(const GemmArgs& g, const f32x4 (
             if (slot < g.cap) g.cand_i[(int64_t)m * g.cap + slot] = g.base + nj;
           } else {
             lse_sum += __builtin_amdgcn_exp2f((sc - t) * g.lse_c);
+          }
+        }
+        else if constexpr (EPI == EPI_FILTER_MASK) {   // FILTER over the allowed rows (the vector path's test)
+          if (!((g.mask[nj >> 5] >> (nj & 31)) & 1u)) continue;
+          const float sc = x * rs * g.cscale[nj];
+          if (sc >= g.theta[(int64_t)m * g.theta_ld]) {
+            const int slot = atomicAdd(g.cnt + m, 1);
+            if (slot < g.cap) {
+              g.cand_s[(int64_t)m * g.cap + slot] = sc;
+              g.cand_i[(int64_t)m * g.cap + slot] = g.base + nj;
+            }
           }
         }
         else {
@@ -180,7 +191,7 @@ __device__ __forceinline__ void epilogue(const GemmArgs& g, const f32x4 (&acc)[B
   float4 cv[C::TN];
 #pragma unroll
   for (int nb = 0; nb < C::TN; ++nb) {
-    if constexpr (!HOIST || EPI == EPI_FILTER || EPI == EPI_RANK || EPI == EPI_LSE) break;   // FILTER / RANK: loaded after the skip test; LSE: per block
+    if constexpr (!HOIST || EPI == EPI_FILTER || EPI == EPI_RANK || EPI == EPI_LSE || EPI == EPI_FILTER_MASK) break;   // FILTER / RANK: loaded after the skip test; LSE: per block
     const int n = wcol + nb * 16;
     if constexpr (EPI == EPI_SCORE || EPI == EPI_FILTER)
       cv[nb] = (g.cscale && n < g.N) ? *(const float4*)(g.cscale + n) : make_float4(1.f, 1.f, 1.f, 1.f);
@@ -313,7 +324,7 @@ __device__ __forceinline__ void epilogue(const GemmArgs& g, const f32x4 (&acc)[B
     for (int mb = 0; mb < C::TM; ++mb) {
       const int m = wrow + mb * 16;
       rs[mb] = (g.rscale && m < g.M) ? g.rscale[m] : 1.f;
-      if constexpr (EPI == EPI_FILTER || EPI == EPI_RANK || EPI == EPI_LSE) th[mb] = m < g.M ? g.theta[(int64_t)m * g.theta_ld] : 0.f;
+      if constexpr (EPI == EPI_FILTER || EPI == EPI_RANK || EPI == EPI_LSE || EPI == EPI_FILTER_MASK) th[mb] = m < g.M ? g.theta[(int64_t)m * g.theta_ld] : 0.f;
     }
     if constexpr (EPI == EPI_LSE) {
       // Log-sum-exp epilogue: th = the row's head floor theta. A score at or above theta - margin
@@ -407,6 +418,66 @@ __device__ __forceinline__ void epilogue(const GemmArgs& g, const f32x4 (&acc)[B
         up += (unsigned)__shfl_xor((int)up, 16, 64);
         up += (unsigned)__shfl_xor((int)up, 32, 64);
         if (lane < 16 && live && up) atomicAdd(g.above + m, up);
+      }
+      return;
+    }
+    if constexpr (EPI == EPI_FILTER_MASK) {
+      // FILTER over the rows a bitset allows. The lane's 4 columns n .. n + 3 (n % 4 == 0) are one
+      // nibble of word n >> 5, which never straddles a word; the nibbles do not depend on the row
+      // block, so they are read once per tile (the words of a tile: BN / 8 bytes, L2-resident).
+      // FILTER's skip test with the mask folded in: a lane without a set bit in a block cannot
+      // append from it, so a block no lane of the wave can append from -- by its bits or by its
+      // largest possible score -- is skipped before its cscale load. Appends are exactly FILTER's
+      // for the columns whose bit is set (same arithmetic, same slot scheme).
+      unsigned nib[C::TN];
+      unsigned any_bits = 0;
+#pragma unroll
+      for (int nb = 0; nb < C::TN; ++nb) {
+        const int n = wcol + nb * 16;
+        nib[nb] = n < g.N ? (g.mask[n >> 5] >> (n & 31)) & 15u : 0u;
+        any_bits |= nib[nb];
+      }
+      if (!__any(any_bits != 0)) return;
+      float cmin = 0.f, cmax = 0.f;
+      bool cok = false;
+      if (g.cbound) {
+        cmin = key_float(g.cbound[0]);
+        cmax = key_float(g.cbound[1]);
+        cok = cmin >= 0.f && cmax <= 3.4028235e38f;   // NaN fails both
+      }
+#pragma unroll
+      for (int mb = 0; mb < C::TM; ++mb) {
+        const int m = wrow + mb * 16;
+        const bool live = m < g.M;
+        const bool rok = cok && rs[mb] >= 0.f && rs[mb] <= 3.4028235e38f && th[mb] >= -3.4028235e38f;
+        float bmx[C::TN];
+        float mx = -3.4028235e38f;
+#pragma unroll
+        for (int nb = 0; nb < C::TN; ++nb) {
+          bmx[nb] = fmaxf(fmaxf(acc[mb][nb][0], acc[mb][nb][1]), fmaxf(acc[mb][nb][2], acc[mb][nb][3]));
+          if (nib[nb]) mx = fmaxf(mx, bmx[nb]);
+        }
+        auto reach = [&](float v) { return live && (!rok || (v * rs[mb]) * (v >= 0.f ? cmax : cmin) >= th[mb]); };
+        if (!__any(any_bits != 0 && reach(mx))) continue;
+#pragma unroll
+        for (int nb = 0; nb < C::TN; ++nb) {
+          if (!__any(nib[nb] != 0 && reach(bmx[nb]))) continue;
+          const int n = wcol + nb * 16;
+          if (!live || !nib[nb]) continue;   // a set bit implies n < N
+          const float4 c = g.cscale ? *(const float4*)(g.cscale + n) : make_float4(1.f, 1.f, 1.f, 1.f);
+          const float sc[4] = {acc[mb][nb][0] * rs[mb] * c.x, acc[mb][nb][1] * rs[mb] * c.y,
+                               acc[mb][nb][2] * rs[mb] * c.z, acc[mb][nb][3] * rs[mb] * c.w};
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            if (((nib[nb] >> j) & 1u) && sc[j] >= th[mb]) {
+              const int slot = atomicAdd(g.cnt + m, 1);
+              if (slot < g.cap) {
+                g.cand_s[(int64_t)m * g.cap + slot] = sc[j];
+                g.cand_i[(int64_t)m * g.cap + slot] = g.base + n + j;
+              }
+            }
+          }
+        }
       }
       return;
     }
@@ -561,7 +632,7 @@ __device__ __forceinline__ void epilogue(const GemmArgs& g, const f32x4 (&acc)[B
 // row-block, TM in all), so it counts TM.
 template <int EPI, int TM, int TN>
 constexpr int epi_min_stores() {
-  return epi_stores16(EPI) ? TM * TN / 2 : (EPI == EPI_FILTER || EPI == EPI_RANK || EPI == EPI_LSE) ? 0 : (EPI == EPI_SCORE && TN == 8) ? TM : TM * TN;
+  return epi_stores16(EPI) ? TM * TN / 2 : (EPI == EPI_FILTER || EPI == EPI_RANK || EPI == EPI_LSE || EPI == EPI_FILTER_MASK) ? 0 : (EPI == EPI_SCORE && TN == 8) ? TM : TM * TN;
 }
 
 }  // namespace gemm_detail

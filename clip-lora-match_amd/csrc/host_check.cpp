@@ -64,6 +64,7 @@ static void argument_checks() {
   CHECK(clm_index_destroy(nullptr) == CLM_OK);
   CHECK(clm_index_size(nullptr) < 0);
   CHECK(clm_index_search(nullptr, nullptr, CLM_F32, 1, 1, nullptr, nullptr, nullptr) != CLM_OK);
+  CHECK(clm_index_search_masked(nullptr, nullptr, CLM_F32, 1, 1, nullptr, 0, nullptr, nullptr, nullptr) == CLM_E_ARG);
   int64_t st[4];
   CHECK(clm_index_stats2(nullptr, st, 4) != CLM_OK);
   CHECK(clm_gemm(0, 99, CLM_EPI_STORE, -1, nullptr, 64, nullptr, 64, 1, 1, 64, nullptr, 1, nullptr, nullptr, nullptr,
@@ -437,6 +438,31 @@ static void device_checks() {
       }
     }
     unsetenv("CLM_SEARCH_BOUNDED");
+  }
+  {   // filtered search on host buffers (every third row allowed, garbage past n in the last word),
+      // every route, against the host reference over the allowed rows
+    std::vector<uint32_t> allow((size_t)(n + 31) / 32, 0u);
+    for (int j = 0; j < n; j += 3) allow[j >> 5] |= 1u << (j & 31);
+    if (n % 32) allow.back() |= ~0u << (n % 32);
+    for (int flag : {0, (int)CLM_MASK_EXACT, (int)CLM_MASK_PASS, (int)CLM_MASK_GATHER}) {
+      CHECK(clm_index_search_masked(idx, q.data(), CLM_F32, nq, k, allow.data(), flag, sc.data(), ix.data(), nullptr) == CLM_OK);
+      for (int i = 0; i < nq; ++i) {
+        std::vector<std::pair<double, int64_t>> all;
+        for (int j = 0; j < n; j += 3) all.push_back({cos64(&q[(size_t)i * dim], &rows[(size_t)j * dim], dim), j});
+        std::sort(all.begin(), all.end(), [](const auto& a, const auto& b) {
+          return a.first > b.first || (a.first == b.first && a.second < b.second);
+        });
+        for (int t = 0; t < k; ++t) {
+          if (t < (int)all.size()) CHECK(ix[(size_t)i * k + t] == all[t].second && sc[(size_t)i * k + t] == (float)all[t].first);
+          else CHECK(ix[(size_t)i * k + t] == -1);
+        }
+      }
+    }
+    int64_t ms[20] = {0};
+    CHECK(clm_index_stats2(idx, ms, 20) == CLM_OK && ms[17] + ms[18] + ms[19] == 4 * (int64_t)nq);
+    CHECK(clm_index_search_masked(idx, q.data(), CLM_F32, nq, k, nullptr, 0, sc.data(), ix.data(), nullptr) == CLM_E_ARG);
+    CHECK(clm_index_search_masked(idx, q.data(), CLM_BF16, nq, k, allow.data(), 0, sc.data(), ix.data(), nullptr) == CLM_E_ARG);
+    CHECK(clm_index_search_masked(idx, q.data(), CLM_F32, nq, 0, allow.data(), 0, sc.data(), ix.data(), nullptr) == CLM_E_ARG);
   }
   CHECK(clm_index_set_offset(idx, 1000) == CLM_OK);
   CHECK(clm_index_search(idx, q.data(), CLM_F32, 1, 1, sc.data(), ix.data(), nullptr) == CLM_OK);

@@ -335,7 +335,7 @@ int pick_config(int epi, int M, int N) {
     forced = e ? atoi(e) : -1;
   }
   // the rank pass exists on the filter's tiles only (config 1 and G2's 8-11)
-  if (epi == EPI_RANK || epi == EPI_LSE) return (forced == 1 || (forced >= 8 && forced <= 11)) ? forced : pick_from(MODELS_G2, M, N);
+  if (epi == EPI_RANK || epi == EPI_LSE || epi == EPI_FILTER_MASK) return (forced == 1 || (forced >= 8 && forced <= 11)) ? forced : pick_from(MODELS_G2, M, N);
   if (forced >= 0 && forced < NCFG) return forced;
   // the search's filter GEMM (K = 512, no stores): G2's loop, 256 x 192 -- configs[4] search
   // 95.9 k QPS vs 86.4 k with gemm_kernel 256 x 256 (profiles/r04_v7_search_cfg_ab.txt)
@@ -372,6 +372,13 @@ hipError_t dispatch(int epi, int id, const GemmArgs& g, hipStream_t s) {
       if constexpr (!BF) {
         if (id == 1) return launch_cfg<false, EPI_LSE, 256, 256, 4, 2, 2>(g, s);
         if (id >= 8 && id <= 11) return gemm2_launch(false, EPI_LSE, id, g, s);
+      }
+      return hipErrorInvalidValue;
+    case EPI_FILTER_MASK:   // as EPI_RANK; the mask words are required
+      if constexpr (!BF) {
+        if (!g.mask) return hipErrorInvalidValue;
+        if (id == 1) return launch_cfg<false, EPI_FILTER_MASK, 256, 256, 4, 2, 2>(g, s);
+        if (id >= 8 && id <= 11) return gemm2_launch(false, EPI_FILTER_MASK, id, g, s);
       }
       return hipErrorInvalidValue;
     default: return hipErrorInvalidValue;

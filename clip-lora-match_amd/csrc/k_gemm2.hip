@@ -233,6 +233,9 @@ hipError_t by_epi(int epi, int id, const GemmArgs& g, hipStream_t s) {
     case EPI_LSE:
       if constexpr (!BF) return by_id<false, EPI_LSE>(id, g, s);
       return hipErrorInvalidValue;
+    case EPI_FILTER_MASK:
+      if constexpr (!BF) return by_id<false, EPI_FILTER_MASK>(id, g, s);
+      return hipErrorInvalidValue;
     default: return hipErrorInvalidValue;
   }
 }

@@ -24,13 +24,6 @@ namespace clm {
 
 namespace {
 
-// threads per row: the largest power of two <= min(64, 16-byte units of one fp16 row)
-int group_of(int dim) {
-  int g = 8;
-  while (g < 64 && g * 2 <= dim / 8) g *= 2;
-  return g;
-}
-
 __device__ __forceinline__ void move_row(const u16* s16, const float* s32, const float* sinv, u16* d16, float* d32,
                                          float* dinv, int64_t src, int64_t dst, int dim, int t, int G) {
   const uint4* a = (const uint4*)(s16 + src * dim);

@@ -21,12 +21,15 @@ enum Epi {
   EPI_RANK = 6,    // s as above against the row's target score t = theta[m]: s > t + rank_margin is
                    // counted into above[m]; otherwise s >= t - rank_margin appends base+n to row m's
                    // band list cand_i (slot from cnt[m], capacity cap). fp16, configs 1 and 8-11 only
-  EPI_LSE = 7      // s as above against the row's head floor theta[m]: s >= theta - rank_margin appends
+  EPI_LSE = 7,     // s as above against the row's head floor theta[m]: s >= theta - rank_margin appends
                    // base+n to row m's band list (cnt / cand_i / cap as EPI_RANK); every other s adds
                    // exp2((s - theta) * lse_c) to the wave's partial lse_part[m * lse_ld + slot], slot =
                    // (column tile) * (wave columns of the config) + wave column < lse_slots(N): every
                    // slot a config uses is written once per live row, the others keep the caller's
                    // zeros. fp16, configs 1 and 8-11 only
+  EPI_FILTER_MASK = 8     // EPI_FILTER over the rows a bitset allows: column n is tested (and its cscale
+                          // loaded) only where bit n & 31 of mask[n >> 5] is set (bits at or past N
+                          // clear: mask_prepare). fp16, configs 1 and 8-11 only
 };
 // upper bound, over the configs EPI_LSE runs on, of the slab slots per row (wave column extents are
 // 64, 96 or 128 index rows)
@@ -65,6 +68,8 @@ struct GemmArgs {
                    // stores, 4 = one tile per workgroup (non-persistent grid)
   // EPI_LSE (with theta = the head floors, rank_margin, cnt / cand_i / cap / base as EPI_RANK)
   float* lse_part; int64_t lse_ld; float lse_c;
+  // EPI_FILTER_MASK (with the EPI_FILTER fields): ceil(N / 32) words, read by that epilogue only
+  const uint32_t* mask;
 };
 
 hipError_t gemm(bool bf16, int epi, const GemmArgs& g, hipStream_t s);
@@ -383,6 +388,43 @@ hipError_t gather_rows(const u16* rows16, const float* rows32, const float* inv,
                        const int64_t* rem, int64_t m, u16* out16, float* out32, float* out_inv, hipStream_t s);
 hipError_t scatter_rows(const u16* src16, const float* src32, const float* src_inv, const int64_t* ids, int64_t offset,
                         int64_t n, int dim, u16* rows16, float* rows32, float* inv, hipStream_t s);
+
+// threads that move one row in the whole-row movers (k_mutate.hip, k_mask.hip): the largest power of
+// two <= min(64, 16-byte units of one fp16 row)
+inline int group_of(int dim) {
+  int g = 8;
+  while (g < 64 && g * 2 <= dim / 8) g *= 2;
+  return g;
+}
+
+// ----------------------------------------------------------- filtered search (k_mask.hip) ---
+// A mask: ceil(N / 32) little-endian u32 words, bit j & 31 of word j >> 5 set iff local row j is
+// allowed. A block of the mask kernels covers MASK_BLOCK_WORDS words (MASK_BLOCK_WORDS * 32 rows).
+constexpr int MASK_BLOCK_WORDS = 256;
+inline int64_t mask_words(int64_t N) { return (N + 31) / 32; }
+inline int64_t mask_blocks(int64_t N) { return (mask_words(N) + MASK_BLOCK_WORDS - 1) / MASK_BLOCK_WORDS; }
+// dst = the caller's words with the bits at or past N cleared; bcnt[b] = block b's set bits
+hipError_t mask_prepare(const uint32_t* src, int64_t N, uint32_t* dst, uint32_t* bcnt, hipStream_t s);
+// boff[b] = the exclusive prefix sum of bcnt over the mask_blocks(N) blocks, boff[blocks] = the total
+// P (int64: one workgroup, fixed order)
+hipError_t mask_scan(const uint32_t* bcnt, int64_t nblocks, int64_t* boff, hipStream_t s);
+// list[boff[b] ..) = block b's set local rows, ascending: the whole list is the allowed rows in order
+// (prefix sums inside the block, no atomics)
+hipError_t mask_compact(const uint32_t* words, int64_t N, const int64_t* boff, uint32_t* list, hipStream_t s);
+// scores [nq, C] (row stride lds), column j = local row r0 + j: -inf where that row's bit is clear; an
+// allowed NaN gets its sign bit cleared (the top-k kernels order scores by their bit pattern)
+hipError_t mask_fill(float* scores, int64_t lds, int64_t nq, int64_t C, int64_t r0, const uint32_t* words,
+                     hipStream_t s);
+// result fix-up over n (score, id) entries. list != null: ids are positions of the allowed list, id =
+// offset + list[id]; list == null: ids are kept. An id < 0 stays -1 and an entry whose score is -inf
+// (the fill value: an exact cosine is finite or NaN) becomes -1.
+hipError_t map_ids(const float* scores, int64_t* ids, int64_t n, const uint32_t* list, int64_t offset, hipStream_t s);
+// out row i = row list[floor(i * P / S)] of the index's arrays (S <= P; S == P: every listed row in
+// order): fp16 rows, inverse norms, and the fp32 rows where rows32 / out32 are given; dim % 8 == 0
+hipError_t mask_gather(const u16* rows16, const float* rows32, const float* inv, int dim, const uint32_t* list,
+                       int64_t P, int64_t S, u16* out16, float* out32, float* out_inv, hipStream_t s);
+// out[i] = value for i < n (floats)
+hipError_t fill_f32(float* out, int64_t n, float value, hipStream_t s);
 
 __host__ __device__ inline unsigned float_key(float f) {
   const unsigned b = __builtin_bit_cast(unsigned, f);

@@ -212,8 +212,26 @@ class ShardedIndex:
         return removed
 
     def search(self, queries: torch.Tensor, k: int,
-               merge: Callable = merge_topk_gpu) -> Tuple[torch.Tensor, torch.Tensor]:
-        s, i = self.local.search(queries, k)
+               merge: Callable = merge_topk_gpu, allow=None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """allow: a row filter over the WHOLE index, the same on every rank -- a bool [n_total] or
+        global ids to keep; each rank applies its slice [start, stop) (CosineIndex.search's allow) and
+        the lists merge as ever. A shard without rows or without an allowed row contributes
+        (-inf, -1) lists."""
+        if allow is None:
+            s, i = self.local.search(queries, k)
+        else:
+            from .search import _allowed_rows
+            a = torch.as_tensor(allow)
+            keep = _allowed_rows(self.n_total, 0, keep=a) if a.dtype == torch.bool else \
+                _allowed_rows(self.n_total, 0, ids=a)
+            mine = keep[self.start: self.stop]
+            if len(self.local) == 0:   # an empty index refuses the call
+                nq = 1 if torch.as_tensor(queries).dim() == 1 else torch.as_tensor(queries).shape[0]
+                dev = getattr(self.local, "device", "cpu")
+                s = torch.full((nq, k), float("-inf"), dtype=torch.float32, device=dev)
+                i = torch.full((nq, k), -1, dtype=torch.int64, device=dev)
+            else:
+                s, i = self.local.search(queries, k, allow=mine)
         if self.world == 1:
             return s, i
         s_all, i_all = gather_candidates(s, i, self.group)

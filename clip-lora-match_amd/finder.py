@@ -200,8 +200,12 @@ class FinderIndex:
         self._unsaved = 0
         print(f"[FinderService] Index updated and saved to: {self.index_path}")
 
-    def search(self, query_emb: torch.Tensor, top_k: int = 5):
-        return self.index.search_with_embedding(query_emb, top_k=top_k)
+    def search(self, query_emb: torch.Tensor, top_k: int = 5, where=None):
+        """where: a row filter (TextSearchIndex.search_with_embedding's allow): a mask, item
+        positions, or a callable (i, image_path, text) -> bool -- only those items compete"""
+        if where is None:
+            return self.index.search_with_embedding(query_emb, top_k=top_k)
+        return self.index.search_with_embedding(query_emb, top_k=top_k, allow=where)
 
 
 __all__ = ["FinderIndex"]

@@ -55,6 +55,35 @@ def _pad_dim(x: torch.Tensor, dim_p: int) -> torch.Tensor:
     return torch.nn.functional.pad(x, (0, dim_p - x.shape[-1]))
 
 
+def pack_mask(keep: torch.Tensor) -> torch.Tensor:
+    """bool [N] -> the ceil(N / 32) little-endian uint32 words of a row filter (bit j & 31 of word
+    j >> 5 = keep[j]; the bits past N clear), stored as int32 on keep's device"""
+    keep = torch.as_tensor(keep).reshape(-1)
+    n = keep.numel()
+    nw = (n + 31) // 32
+    bits = torch.zeros((nw * 32,), dtype=torch.int64, device=keep.device)
+    bits[:n] = keep.to(torch.int64)
+    w = (bits.view(nw, 32) << torch.arange(32, dtype=torch.int64, device=keep.device)).sum(1)
+    return torch.where(w >= 2 ** 31, w - 2 ** 32, w).to(torch.int32)
+
+
+def _allowed_rows(n: int, offset: int, keep=None, ids=None, exclude=None, device=None) -> torch.Tensor:
+    """bool [n] (local row order) from a bool [n], global ids to keep, or global ids to exclude"""
+    if keep is not None:
+        k = torch.as_tensor(keep).reshape(-1)
+        if k.dtype != torch.bool or k.numel() != n:
+            raise ValueError(f"keep must be a bool tensor of {n} rows, got {k.dtype} x {k.numel()}")
+        return k.to(device)
+    g = torch.as_tensor(ids if ids is not None else exclude).reshape(-1).to(device=device, dtype=torch.int64)
+    loc = g - int(offset)
+    if g.numel() and (int(loc.min()) < 0 or int(loc.max()) >= n):
+        raise ValueError(f"a row id is outside the index [{int(offset)}, {int(offset) + n})")
+    out = torch.zeros((n,), dtype=torch.bool, device=device) if ids is not None else \
+        torch.ones((n,), dtype=torch.bool, device=device)
+    out[loc] = ids is not None
+    return out
+
+
 class CosineIndex:
     """GPU index of fp16 rows + fp32 inverse norms (score = q.row / (|q| |row|))."""
 
@@ -130,8 +159,15 @@ class CosineIndex:
         C.check(C.lib().clm_index_read(self._h, start, n, C.ptr(out), C.stream_of(self.device)), "clm_index_read")
         return out[:, :self.dim]
 
-    def search(self, queries, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
-        """queries [nq, dim] (f32/f16, any device) -> (scores [nq,k] f32, idx [nq,k] i64) on the GPU."""
+    def search(self, queries, k: int, allow=None, route: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+        """queries [nq, dim] (f32/f16, any device) -> (scores [nq,k] f32, idx [nq,k] i64) on the GPU.
+        allow: a row filter -- the first k of the ALLOWED rows in the same order, the same exact
+        scores, (-inf, -1) past the number of allowed rows (clm_index_search_masked). Told apart by
+        dtype: a bool [N], int64 global ids to keep (a list of ints), or the int32 / uint32 word
+        tensor of allow_mask(); any other dtype is a TypeError (_allow_words). route: 0, or
+        C.CLM_MASK_EXACT / _PASS / _GATHER to ask for a route (the results do not depend on it)."""
+        if allow is not None:
+            return self._search_masked(queries, k, allow, route)
         q = torch.as_tensor(queries)
         if q.dim() == 1:
             q = q.unsqueeze(0)
@@ -147,6 +183,56 @@ class CosineIndex:
         C.check(C.lib().clm_index_search(self._h, C.ptr(q), code, nq, int(k), C.ptr(s), C.ptr(i),
                                          C.stream_of(self.device)), "clm_index_search")
         return s, i
+
+    # -------------------------------------------------------- filtered search --
+    def allow_mask(self, keep=None, ids=None, exclude=None) -> torch.Tensor:
+        """The device word tensor of a row filter (int32 storage of the ceil(N / 32) little-endian
+        uint32 words: bit j & 31 of word j >> 5 = local row j is allowed), from exactly one of
+        keep (bool [N], local row order), ids (global ids to keep) or exclude (global ids to drop).
+        ValueError for an id outside the index. Torch ops only; reusable across searches until the
+        index's rows change."""
+        if sum(a is not None for a in (keep, ids, exclude)) != 1:
+            raise ValueError("allow_mask takes exactly one of keep, ids, exclude")
+        return pack_mask(_allowed_rows(len(self), getattr(self, "_offset", 0), keep, ids, exclude, self.device))
+
+    def _allow_words(self, allow) -> torch.Tensor:
+        """The word tensor of an `allow` argument, told apart by dtype alone: bool = keep [N]; int64 (what
+        a Python list of ints or torch.nonzero gives) = global ids to keep; int32 / uint32 = mask words
+        as allow_mask() returns them. Anything else (floats, other integer widths) is a TypeError, so
+        ids are never read as words by accident: convert them to int64 or call allow_mask(ids=)."""
+        a = torch.as_tensor(allow)
+        if isinstance(allow, (list, tuple)) and len(allow) == 0:   # no ids (an empty list has no integer dtype)
+            a = a.to(torch.int64)
+        if a.dtype == torch.bool:
+            return self.allow_mask(keep=a)
+        if a.dtype == torch.int64:
+            return self.allow_mask(ids=a)
+        if a.dtype in (torch.int32, torch.uint32):
+            return a.to(self.device).contiguous()
+        raise TypeError(f"allow must be bool (keep), int64 (ids) or int32 / uint32 (mask words), got {a.dtype}")
+
+    def _search_masked(self, queries, k: int, allow, route: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+        q = self._queries(queries)
+        nq, n = q.shape[0], len(self)
+        a = self._allow_words(allow)
+        if a.numel() != (n + 31) // 32:
+            raise ValueError(f"allow: an int32 / uint32 tensor is read as mask words, and a mask of {n} rows holds "
+                             f"{(n + 31) // 32} of them, got {a.numel()} (ids go as int64 or through allow_mask(ids=))")
+        s = torch.empty((nq, k), dtype=torch.float32, device=self.device)
+        i = torch.empty((nq, k), dtype=torch.int64, device=self.device)
+        code = C.CLM_F32 if q.dtype == torch.float32 else C.CLM_F16
+        C.check(C.lib().clm_index_search_masked(self._h, C.ptr(q) if nq else None, code, nq, int(k),
+                                                C.ptr(a) if nq else None, int(route), C.ptr(s) if nq else None,
+                                                C.ptr(i) if nq else None, C.stream_of(self.device)),
+                "clm_index_search_masked")
+        return s, i
+
+    def mask_stats(self) -> dict:
+        """filtered-search queries served by the MFMA pass route (`pass`), the gather route (`gather`)
+        and the exact route (`exact`; a pass-route query redone exactly counts here)"""
+        v = (ctypes.c_int64 * 20)()
+        C.check(C.lib().clm_index_stats2(self._h, v, 20))
+        return {"pass": v[17], "gather": v[18], "exact": v[19]}
 
     # ------------------------------------------------------------------ ranks --
     def _queries(self, queries) -> torch.Tensor:
@@ -544,8 +630,18 @@ class TextSearchIndex:
         self._n = self._host.shape[0] if self._host.dim() >= 1 else 0
 
     # --------------------------------------------------------------- search --
-    def search_batch(self, queries, top_k: int = 5) -> Tuple[torch.Tensor, torch.Tensor]:
-        """[nq, d] queries -> (scores [nq, k], indices [nq, k]) on the GPU, k = min(top_k, num_items)."""
+    def _allow(self, allow):
+        """a row filter for the GPU index: a mask / bool / ids as CosineIndex.search takes them, or a
+        callable (i, image_path, text) -> bool evaluated over the host metadata"""
+        if callable(allow):
+            keep = [bool(allow(i, self.image_paths[i] if i < len(self.image_paths) else "",
+                               self.texts[i] if i < len(self.texts) else "")) for i in range(self.num_items)]
+            return torch.tensor(keep, dtype=torch.bool)
+        return allow
+
+    def search_batch(self, queries, top_k: int = 5, allow=None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """[nq, d] queries -> (scores [nq, k], indices [nq, k]) on the GPU, k = min(top_k, num_items).
+        allow: only these rows compete (see _allow); slots past their number hold (-inf, -1)."""
         k = min(int(top_k), self.num_items)
         if k < 0:
             raise RuntimeError("selected index k out of range")
@@ -553,10 +649,13 @@ class TextSearchIndex:
             q = torch.as_tensor(queries)
             nq = 1 if q.dim() == 1 else q.shape[0]
             return torch.empty((nq, 0)), torch.empty((nq, 0), dtype=torch.int64)
+        if allow is not None:
+            return self._gpu.search(queries, k, allow=self._allow(allow))
         return self._gpu.search(queries, k)
 
-    def search_with_embedding(self, query_emb: torch.Tensor, top_k: int = 5) -> List[SearchResult]:
-        """query_emb: shape (d,) atau (1, d)."""
+    def search_with_embedding(self, query_emb: torch.Tensor, top_k: int = 5, allow=None) -> List[SearchResult]:
+        """query_emb: shape (d,) atau (1, d). allow: a row filter (search_batch); fewer than top_k
+        results when fewer rows are allowed."""
         query_emb = torch.as_tensor(query_emb)
         if query_emb.ndim == 1:
             query_emb = query_emb.unsqueeze(0)
@@ -564,9 +663,14 @@ class TextSearchIndex:
             raise ValueError(f"query_emb must be shape (d,) or (1, d), got {tuple(query_emb.shape)}")
         if query_emb.shape[-1] != self.dim:
             raise ValueError(f"query_emb dim {query_emb.shape[-1]} != index dim {self.dim}")
-        scores, indices = self.search_batch(query_emb, top_k)
+        if allow is None:   # today's call, untouched
+            scores, indices = self.search_batch(query_emb, top_k)
+        else:
+            scores, indices = self.search_batch(query_emb, top_k, allow=allow)
         results: List[SearchResult] = []
         for idx, score in zip(indices[0].tolist(), scores[0].tolist()):
+            if allow is not None and idx < 0:   # the pad of a short filtered list
+                continue
             # an index outside [0, len) has no metadata: the (-inf, -1) pad of a short result must
             # not read the last item's through Python's negative indexing
             img = self.image_paths[idx] if 0 <= idx < len(self.image_paths) else ""
@@ -574,13 +678,14 @@ class TextSearchIndex:
             results.append(SearchResult(index=idx, score=float(score), image_path=img, text=txt))
         return results
 
-    def search_by_text(self, query, model, processor, device, top_k: int = 5) -> List[SearchResult]:
+    def search_by_text(self, query, model, processor, device, top_k: int = 5, allow=None) -> List[SearchResult]:
         from .clip_model import encode_text
-        return self.search_with_embedding(encode_text(query, model, processor, device), top_k=top_k)
+        return self.search_with_embedding(encode_text(query, model, processor, device), top_k=top_k, allow=allow)
 
-    def search_by_image(self, image_path, model, processor, device, top_k: int = 5) -> List[SearchResult]:
+    def search_by_image(self, image_path, model, processor, device, top_k: int = 5, allow=None) -> List[SearchResult]:
         from .clip_model import encode_image
-        return self.search_with_embedding(encode_image(image_path, model, processor, device), top_k=top_k)
+        return self.search_with_embedding(encode_image(image_path, model, processor, device), top_k=top_k,
+                                          allow=allow)
 
     def search_above_with_embedding(self, query_emb: torch.Tensor, threshold: float) -> List[SearchResult]:
         """Every item whose cosine with the query is >= threshold (CosineIndex.search_above), best

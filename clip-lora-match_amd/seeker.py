@@ -81,8 +81,9 @@ def build_query_embedding(query_text, query_image_path: Optional[Union[str, Path
 
 def search_items(index: TextSearchIndex, model, processor, device, query_text=None,
                  query_image_path: Optional[Union[str, Path]] = None, top_k: int = 5,
-                 root_dir: Optional[Union[str, Path]] = None) -> List[SearchResult]:
+                 root_dir: Optional[Union[str, Path]] = None, allow=None) -> List[SearchResult]:
     """SeekerService.search_items (seeker_service.py:159-186) against a resident index.
+    allow: a row filter, forwarded to TextSearchIndex.search_with_embedding.
 
     A relative `query_image_path` is resolved under `root_dir` (the service's root, :173);
     a missing image raises FileNotFoundError (:174-175).
@@ -94,7 +95,9 @@ def search_items(index: TextSearchIndex, model, processor, device, query_text=No
         if not img_path.exists():
             raise FileNotFoundError(f"Query image not found: {img_path}")
     q = build_query_embedding(query_text, img_path, model, processor, device)
-    return index.search_with_embedding(q, top_k=top_k)
+    if allow is None:
+        return index.search_with_embedding(q, top_k=top_k)
+    return index.search_with_embedding(q, top_k=top_k, allow=allow)
 
 
 __all__ = ["fuse_query_embeddings", "build_query_embedding", "search_items"]

@@ -330,12 +330,44 @@ int clm_index_search_above_rows(clm_index* idx, int64_t row0, int64_t nrows, con
 int clm_index_search_above_read(clm_index* idx, int64_t start, int64_t n, float* out_scores, int64_t* out_idx,
                                 void* stream);
 
+/* Filtered search: exact top-k over an allowed subset of the rows. allow: ceil(size / 32)
+ * little-endian uint32 words, bit j & 31 of word j >> 5 set iff local row j (global id offset + j)
+ * is allowed; bits at or past size in the last word are ignored. The result of query i is the first
+ * k entries of the ALLOWED rows in the search order (exact score desc, global id asc, NaN above every
+ * number), scores bit for bit clm_index_search's; slots past the number of allowed rows hold
+ * (-inf, -1). So an all-ones mask returns what clm_index_search returns, the result equals
+ * clm_index_search on an index holding only the allowed rows in order (positions mapped back to ids),
+ * and the results of row shards merge with clm_topk_merge.
+ * Three routes, the same bits on each: exact (windows of exact scores, disallowed entries set to
+ * -inf, the exact scan's top-k; k <= 1024), gather (the allowed rows' operands gathered into a
+ * temporary index of P x (6 dim + 4) bytes, P = the allowed rows, searched as clm_index_search does,
+ * positions mapped back; any k) and pass (a sample of the allowed rows gives each query a threshold,
+ * one fp16 MFMA pass lists the allowed rows that reach it, they are re-scored exactly; k <= 256, finite
+ * row norms, dim <= 8192). flags: 0 = chosen by size, k and P; CLM_MASK_EXACT / _PASS / _GATHER ask
+ * for a route, which is taken when its preconditions hold (clm_index_stats2 says which route served).
+ * An index holding a zero or non-finite row norm (NaN scores) is served by the exact route while
+ * k <= 1024, as is a single NaN-scoring query of the other routes; for k > 1024 NaN scores are placed
+ * as clm_index_search places them. Mind the cost: the exact route computes all nq x size cosines in
+ * fp64 (about 2 ms per query per 1 M rows of 512 dims), so one zero row in a large index makes every
+ * filtered search of it that slow -- remove or replace such rows (clm_index_remove / _update).
+ * Otherwise the exact scan over all rows is taken only on request, for dim > 8192 or under
+ * $CLM_SEARCH_FULL=1; small problems go through the gather route, whose temporary index takes the
+ * exact scan up to 2^20 cosines.
+ * The call keeps no state: it leaves a held threshold-search result and the cached row sample of the
+ * unmasked search as they are. q [nq, dim] CLM_F32|CLM_F16; every pointer host or device; k >= 1.
+ * CLM_E_ARG: a null index, q, allow or output with nq > 0, a dtype other than f32 / f16, nq < 0, an
+ * empty index. CLM_E_OOM: the gather route's buffers cannot be allocated (clm_last_error names the
+ * row count). */
+enum { CLM_MASK_EXACT = 1 << 30, CLM_MASK_PASS = 1 << 29, CLM_MASK_GATHER = 1 << 28 };
+int clm_index_search_masked(clm_index* idx, const void* q, int q_dtype, int64_t nq, int k,
+                            const uint32_t* allow, int flags, float* out_scores, int64_t* out_idx, void* stream);
+
 /* search-path counters since creation: queries served by the sampled single-pass bounded
  * search (`filtered`), by the exact scan or the fp16-scan-bounded search (`exact`), and
  * bounded queries whose candidate list overflowed (redone by a whole-list pass, or by the exact
  * scan when the list is longer than 8192 / k chunks of 4096) */
 int clm_index_stats(const clm_index* idx, int64_t* filtered, int64_t* exact, int64_t* overflow);
-/* out[0..n), n <= 17: sampled bounded, fp16-scan bounded, full exact scan, overflow re-runs, then the
+/* out[0..n), n <= 20: sampled bounded, fp16-scan bounded, full exact scan, overflow re-runs, then the
  * sampled queries whose filter pass ran on the G2 256 x 192 tiles / on gemm_kernel 256 x 256 (chosen
  * per query block from the block's sampled candidate counts: near-duplicate blocks take the latter),
  * then the queries served by the small-batch streaming search (nq <= 16 on a large index: one pass
@@ -344,7 +376,9 @@ int clm_index_stats(const clm_index* idx, int64_t* filtered, int64_t* exact, int
  * the band rows re-scored for the band-served queries, then the clm_index_lse queries served by the
  * fast route, by the exact route (clm_index_lse64's among them), and those whose band list overflowed
  * its capacity, then the threshold-search queries served by the MFMA pass, by the exact route, and
- * those whose candidate list overflowed its capacity */
+ * those whose candidate list overflowed its capacity, then the clm_index_search_masked queries served
+ * by the pass route, by the gather route and by the exact route (a pass-route query redone exactly
+ * counts as exact) */
 int clm_index_stats2(const clm_index* idx, int64_t* out, int n);
 
 /* full cosine matrix, exact: out [nq, n] f32 = fp32(cos64(q_i, c_j)), any dim */
