@@ -126,6 +126,11 @@ def lib():
         "clm_gemm": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int,
                              c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
         "clm_gemm_num_configs": (c_int, []),
+        "clm_gemm_select": (c_int, [c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int,
+                                    c_void_p, c_void_p, c_void_p, c_int64, c_float, c_void_p, c_void_p, c_void_p,
+                                    c_int, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_void_p, c_int,
+                                    c_void_p]),
+        "clm_value_bounds": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_void_p]),
         "clm_debug_set": (None, [c_int]),
         "clm_attention": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p]),
         "clm_gemm_scores16": (c_int, [c_int, c_int, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int,
@@ -178,9 +183,11 @@ EXPORTED = (
     "clm_layernorm_ex", "clm_gemm_ex", "clm_patchify", "clm_write_cls", "clm_gather_pooled", "clm_pool_project",
     "clm_index_search_above", "clm_index_search_above_rows", "clm_index_search_above_read",
     "clm_index_search_masked",
+    "clm_gemm_select", "clm_value_bounds",
 )
 CLM_EPI_STORE, CLM_EPI_GELU, CLM_EPI_RESID, CLM_EPI_SCORE = 0, 1, 2, 4
 CLM_EPI_PATCH = 3   # clm_gemm_ex only
+CLM_EPI_FILTER, CLM_EPI_RANK, CLM_EPI_LSE, CLM_EPI_FILTER_MASK = 5, 6, 7, 8   # clm_gemm_select only
 CLM_PROF_GEMM, CLM_PROF_ATTN, CLM_PROF_LN, CLM_PROF_OTHER = 0, 1, 2, 3
 
 

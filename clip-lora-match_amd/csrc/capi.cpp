@@ -873,6 +873,50 @@ int clm_gemm_scores16(int hip_device, int config, const void* A, int64_t lda, co
   return CLM_OK;
 }
 
+// test hook: the index passes' selecting epilogues alone (EPI_FILTER / EPI_RANK / EPI_LSE /
+// EPI_FILTER_MASK, gemm_common.hpp), with every GemmArgs field the search sets for them. Nothing is
+// zeroed here: cnt, above and the slab are the caller's, as in the search.
+int clm_gemm_select(int hip_device, int epilogue, int config, const void* A, int64_t lda, const void* W, int64_t ldw,
+                    int M, int N, int K, const float* rscale, const float* cscale, const float* theta,
+                    int64_t theta_ld, float margin, int* cnt, float* cand_s, int64_t* cand_i, int cap, int64_t base,
+                    const uint32_t* cbound, uint32_t* above, float* lse_part, int64_t lse_ld, float lse_c,
+                    const uint32_t* mask, int m_fastest, void* stream) {
+  if (epilogue != EPI_FILTER && epilogue != EPI_RANK && epilogue != EPI_LSE && epilogue != EPI_FILTER_MASK)
+    return fail(CLM_E_ARG, "gemm_select: epilogue must be FILTER, RANK, LSE or FILTER_MASK");
+  if (config >= gemm_num_configs()) return fail(CLM_E_ARG, "bad config");
+  if (M < 0 || N < 0 || K <= 0 || K % 64 || lda % 8 || ldw % 8 || lda < K || ldw < K)
+    return fail(CLM_E_ARG, "bad shape (K % 64 == 0; lda, ldw multiples of 8 and >= K)");
+  if (cap < 1 || theta_ld < 1) return fail(CLM_E_ARG, "gemm_select: cap >= 1 and theta_ld >= 1");
+  if (epilogue == EPI_LSE && lse_ld < lse_slots(N)) return fail(CLM_E_ARG, "gemm_select: lse_ld < N / 64 + 4");
+  if (M == 0 || N == 0) return CLM_OK;
+  if (!A || !W || !cscale || !theta || !cnt || !cand_i) return fail(CLM_E_ARG, "gemm_select: null pointer");
+  if ((epilogue == EPI_FILTER || epilogue == EPI_FILTER_MASK) && !cand_s)
+    return fail(CLM_E_ARG, "gemm_select: FILTER / FILTER_MASK write cand_s");
+  if (epilogue == EPI_RANK && !above) return fail(CLM_E_ARG, "gemm_select: RANK counts into above");
+  if (epilogue == EPI_LSE && !lse_part) return fail(CLM_E_ARG, "gemm_select: LSE writes lse_part");
+  if (epilogue == EPI_FILTER_MASK && !mask) return fail(CLM_E_ARG, "gemm_select: FILTER_MASK reads mask");
+  DeviceGuard g(hip_device);
+  GemmArgs a{};
+  a.A = (const u16*)A; a.lda = lda; a.W = (const u16*)W; a.ldw = ldw; a.M = M; a.N = N; a.K = K;
+  a.rscale = rscale; a.cscale = cscale; a.theta = theta; a.theta_ld = theta_ld; a.rank_margin = margin;
+  a.cnt = cnt; a.cand_s = cand_s; a.cand_i = cand_i; a.cap = cap; a.base = base; a.cbound = cbound;
+  a.above = above; a.lse_part = lse_part; a.lse_ld = lse_ld; a.lse_c = lse_c; a.mask = mask;
+  a.m_fastest = m_fastest ? 1 : 0;
+  a.debug = g_gemm_debug;
+  hipError_t e = gemm_cfg(false, epilogue, config, a, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(CLM_E_HIP, std::string("gemm: ") + hipGetErrorString(e));
+  return CLM_OK;
+}
+
+// test hook: the order keys of min / max cscale (value_bounds, k_search.hip), the cbound of the index passes
+int clm_value_bounds(int hip_device, const float* v, int64_t n, uint32_t* keys, void* stream) {
+  if (n < 0 || !keys || (n > 0 && !v)) return fail(CLM_E_ARG, "value_bounds: n >= 0, keys, and v where n > 0");
+  DeviceGuard g(hip_device);
+  hipError_t e = value_bounds(v, n, keys, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(CLM_E_HIP, std::string("value_bounds: ") + hipGetErrorString(e));
+  return CLM_OK;
+}
+
 void clm_debug_set(int flags) { g_gemm_debug = flags; }
 
 int clm_attention_ex(int hip_device, int dtype, int flags, const void* qkv, void* out, int64_t ldo, int B, int T,

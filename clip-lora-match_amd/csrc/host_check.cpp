@@ -205,6 +205,61 @@ static void argument_checks() {
                       nullptr) == CLM_E_HIP);   // N % 4
     CHECK(clm_gemm_ex(0, CLM_F16, CLM_EPI_STORE, -1, nullptr, 64, nullptr, 64, 0, 4, 64, nullptr, 4, nullptr, nullptr,
                       0, 0, nullptr, 0, nullptr, nullptr) == CLM_OK);   // M = 0
+    {   // the selecting epilogues' hook and the cscale bounds: refused (or empty) before any launch
+      int64_t ci[1] = {0};
+      uint32_t u[2] = {0u, 0u};
+      // clm_gemm_select(dev, epi, config, A, lda, W, ldw, M, N, K, rscale, cscale, theta, theta_ld, margin, cnt,
+      //                 cand_s, cand_i, cap, base, cbound, above, lse_part, lse_ld, lse_c, mask, m_fastest, stream)
+      auto sel = [&](int epi, int cfg, const void* A, int64_t lda, const void* W, int64_t ldw, int M, int N, int K,
+                     const float* cs, const float* th, int64_t theta_ld, int* cnt, float* cand_s, int64_t* cand_i,
+                     int cap, uint32_t* above, float* slab, int64_t lse_ld, const uint32_t* mask) {
+        return clm_gemm_select(0, epi, cfg, A, lda, W, ldw, M, N, K, nullptr, cs, th, theta_ld, 0.f, cnt, cand_s, cand_i,
+                               cap, 0, nullptr, above, slab, lse_ld, 1.f, mask, 1, nullptr);
+      };
+      CHECK(sel(CLM_EPI_SCORE, -1, x, 64, x, 64, 1, 1, 64, f, f, 1, one, f, ci, 1, u, f, 4, u) == CLM_E_ARG);   // epilogue
+      CHECK(sel(9, -1, x, 64, x, 64, 1, 1, 64, f, f, 1, one, f, ci, 1, u, f, 4, u) == CLM_E_ARG);
+      CHECK(sel(CLM_EPI_FILTER, 99, x, 64, x, 64, 1, 1, 64, f, f, 1, one, f, ci, 1, u, f, 4, u) == CLM_E_ARG);   // config
+      CHECK(sel(CLM_EPI_FILTER, -1, x, 64, x, 64, -1, 1, 64, f, f, 1, one, f, ci, 1, u, f, 4, u) == CLM_E_ARG);  // M < 0
+      CHECK(sel(CLM_EPI_FILTER, -1, x, 64, x, 64, 1, -1, 64, f, f, 1, one, f, ci, 1, u, f, 4, u) == CLM_E_ARG);  // N < 0
+      CHECK(sel(CLM_EPI_FILTER, -1, x, 64, x, 64, 1, 1, 0, f, f, 1, one, f, ci, 1, u, f, 4, u) == CLM_E_ARG);    // K <= 0
+      CHECK(sel(CLM_EPI_FILTER, -1, x, 96, x, 96, 1, 1, 96, f, f, 1, one, f, ci, 1, u, f, 4, u) == CLM_E_ARG);   // K % 64
+      CHECK(sel(CLM_EPI_FILTER, -1, x, 68, x, 64, 1, 1, 64, f, f, 1, one, f, ci, 1, u, f, 4, u) == CLM_E_ARG);   // lda % 8
+      CHECK(sel(CLM_EPI_FILTER, -1, x, 64, x, 68, 1, 1, 64, f, f, 1, one, f, ci, 1, u, f, 4, u) == CLM_E_ARG);   // ldw % 8
+      CHECK(sel(CLM_EPI_FILTER, -1, x, 64, x, 128, 1, 1, 128, f, f, 1, one, f, ci, 1, u, f, 4, u) == CLM_E_ARG); // lda < K
+      CHECK(sel(CLM_EPI_FILTER, -1, x, 128, x, 64, 1, 1, 128, f, f, 1, one, f, ci, 1, u, f, 4, u) == CLM_E_ARG); // ldw < K
+      CHECK(sel(CLM_EPI_FILTER, -1, x, 64, x, 64, 1, 1, 64, f, f, 1, one, f, ci, 0, u, f, 4, u) == CLM_E_ARG);   // cap < 1
+      CHECK(sel(CLM_EPI_FILTER, -1, x, 64, x, 64, 1, 1, 64, f, f, 0, one, f, ci, 1, u, f, 4, u) == CLM_E_ARG);   // theta_ld < 1
+      CHECK(sel(CLM_EPI_LSE, -1, x, 64, x, 64, 1, 1, 64, f, f, 1, one, f, ci, 1, u, f, 3, u) == CLM_E_ARG);   // lse_ld < 4
+      CHECK(sel(CLM_EPI_LSE, -1, x, 64, x, 64, 1, 640, 64, f, f, 1, one, f, ci, 1, u, f, 13, u) == CLM_E_ARG);   // < 640 / 64 + 4
+      CHECK(sel(CLM_EPI_FILTER, -1, nullptr, 64, x, 64, 1, 1, 64, f, f, 1, one, f, ci, 1, u, f, 4, u) == CLM_E_ARG);   // A
+      CHECK(sel(CLM_EPI_FILTER, -1, x, 64, nullptr, 64, 1, 1, 64, f, f, 1, one, f, ci, 1, u, f, 4, u) == CLM_E_ARG);   // W
+      CHECK(sel(CLM_EPI_FILTER, -1, x, 64, x, 64, 1, 1, 64, nullptr, f, 1, one, f, ci, 1, u, f, 4, u) == CLM_E_ARG);   // cscale
+      CHECK(sel(CLM_EPI_FILTER, -1, x, 64, x, 64, 1, 1, 64, f, nullptr, 1, one, f, ci, 1, u, f, 4, u) == CLM_E_ARG);   // theta
+      CHECK(sel(CLM_EPI_FILTER, -1, x, 64, x, 64, 1, 1, 64, f, f, 1, nullptr, f, ci, 1, u, f, 4, u) == CLM_E_ARG);     // cnt
+      CHECK(sel(CLM_EPI_FILTER, -1, x, 64, x, 64, 1, 1, 64, f, f, 1, one, f, nullptr, 1, u, f, 4, u) == CLM_E_ARG);    // cand_i
+      CHECK(sel(CLM_EPI_FILTER, -1, x, 64, x, 64, 1, 1, 64, f, f, 1, one, nullptr, ci, 1, u, f, 4, u) == CLM_E_ARG);   // cand_s
+      CHECK(sel(CLM_EPI_FILTER_MASK, -1, x, 64, x, 64, 1, 1, 64, f, f, 1, one, nullptr, ci, 1, u, f, 4, u) == CLM_E_ARG);
+      CHECK(sel(CLM_EPI_FILTER_MASK, -1, x, 64, x, 64, 1, 1, 64, f, f, 1, one, f, ci, 1, u, f, 4, nullptr) == CLM_E_ARG);   // mask
+      CHECK(sel(CLM_EPI_RANK, -1, x, 64, x, 64, 1, 1, 64, f, f, 1, one, nullptr, ci, 1, nullptr, f, 4, u) == CLM_E_ARG);    // above
+      CHECK(sel(CLM_EPI_LSE, -1, x, 64, x, 64, 1, 1, 64, f, f, 1, one, nullptr, ci, 1, u, nullptr, 4, u) == CLM_E_ARG);     // slab
+      // what the launcher refuses, before any launch: a tile without the epilogue
+      CHECK(sel(CLM_EPI_FILTER, 13, x, 128, x, 128, 1, 8, 128, f, f, 1, one, f, ci, 1, u, f, 4, u) == CLM_E_HIP);
+      CHECK(sel(CLM_EPI_FILTER, 14, x, 128, x, 128, 1, 8, 128, f, f, 1, one, f, ci, 1, u, f, 4, u) == CLM_E_HIP);
+      for (int cfg : {0, 2, 3, 4, 5, 6, 7, 12, 13, 14}) {
+        CHECK(sel(CLM_EPI_RANK, cfg, x, 128, x, 128, 1, 8, 128, f, f, 1, one, nullptr, ci, 1, u, f, 4, u) == CLM_E_HIP);
+        CHECK(sel(CLM_EPI_LSE, cfg, x, 128, x, 128, 1, 8, 128, f, f, 1, one, nullptr, ci, 1, u, f, 4, u) == CLM_E_HIP);
+        CHECK(sel(CLM_EPI_FILTER_MASK, cfg, x, 128, x, 128, 1, 8, 128, f, f, 1, one, f, ci, 1, u, f, 4, u) == CLM_E_HIP);
+      }
+      // nothing to do: M == 0 or N == 0, whatever the pointers
+      CHECK(sel(CLM_EPI_FILTER, -1, nullptr, 64, nullptr, 64, 0, 4, 64, nullptr, nullptr, 1, nullptr, nullptr, nullptr, 1,
+                nullptr, nullptr, 0, nullptr) == CLM_OK);
+      CHECK(sel(CLM_EPI_LSE, -1, nullptr, 64, nullptr, 64, 4, 0, 64, nullptr, nullptr, 1, nullptr, nullptr, nullptr, 1,
+                nullptr, nullptr, 4, nullptr) == CLM_OK);
+      // clm_value_bounds(dev, v, n, keys, stream)
+      CHECK(clm_value_bounds(0, f, -1, u, nullptr) == CLM_E_ARG);
+      CHECK(clm_value_bounds(0, f, 4, nullptr, nullptr) == CLM_E_ARG);
+      CHECK(clm_value_bounds(0, nullptr, 4, u, nullptr) == CLM_E_ARG);
+    }
     // clm_patchify(dev, dtype, pix, layout, B, S, p, C, lut, P, Kp, stream)
     CHECK(clm_patchify(0, CLM_F32, x, CLM_PIX_U8_HWC, 1, 16, 8, 3, f, x, 192, nullptr) == CLM_E_ARG);   // dtype
     CHECK(clm_patchify(0, CLM_F16, x, 7, 1, 16, 8, 3, f, x, 192, nullptr) == CLM_E_ARG);                // layout

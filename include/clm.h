@@ -416,8 +416,45 @@ int clm_gemm_num_configs(void);
 int clm_gemm_scores16(int hip_device, int config, const void* A, int64_t lda, const void* W, int64_t ldw, int M,
                       int N, int K, const float* rscale, const float* cscale, void* out, int64_t ldo, int mode,
                       void* stream);
+/* clm_gemm_select: the GEMM whose epilogue selects instead of storing, as every index pass runs it
+ * (test hook; fp16 A [M, lda] / W [N, ldw], device pointers; every extent is the caller's to provide).
+ * s = acc * rscale[m] * cscale[n] (rscale NULL: 1), t = theta[m * theta_ld], id = base + n:
+ *   CLM_EPI_FILTER       s >= t: (s, id) appended to row m's list cand_s / cand_i [M, cap];
+ *   CLM_EPI_FILTER_MASK  the same over the columns whose bit n & 31 of mask[n >> 5] is set; mask holds
+ *                        ceil(N / 32) words; the bits at or past N of the last word are not read;
+ *   CLM_EPI_RANK         s > t + margin counted into above[m]; otherwise s >= t - margin: id appended;
+ *   CLM_EPI_LSE          s >= t - margin: id appended; every other column adds exp2((s - t) * lse_c) to
+ *                        one slot of lse_part [M, lse_ld >= N / 64 + 4]: slot (n / BN) * WN + wave column
+ *                        of the config's BN-wide tile with WN wave columns (config 1: 128 columns per
+ *                        slot, 8: 96, 9 / 10 / 11: 64). The slots ceil(N / BN) * WN of a row m < M are
+ *                        each stored once (a slot none of whose columns is below N holds 0), the others
+ *                        are not touched. A NaN score makes its slot NaN.
+ * Appends go to slot atomicAdd(cnt[m], 1) while that is below cap, in no fixed order; cnt[m] counts them
+ * all, stored or not. cand_s is unused by RANK / LSE. A NaN score or threshold selects nothing (RANK:
+ * neither counted nor listed). Nothing is zeroed: cnt, above and lse_part are the caller's, and rows at
+ * or past M of every output are untouched.
+ * cbound (or NULL: no skip test): the 2 keys of clm_value_bounds(cscale, N); FILTER / FILTER_MASK / RANK
+ * then skip the 16 x 16 blocks whose largest possible score is below the threshold -- the selected
+ * (s, id) sets are the same. m_fastest: 0 = the grouped tile order of clm_gemm, non-0 = the index passes'
+ * (consecutive workgroups walk M); the results do not depend on it. config as clm_gemm (-1: heuristic):
+ * FILTER runs on configs 0-12, the others on 1 and 8-11; anything else is CLM_E_HIP with nothing written.
+ * CLM_E_ARG, before any launch: an epilogue outside the four, config >= clm_gemm_num_configs(), M or N < 0,
+ * K <= 0 or K % 64, lda / ldw not a multiple of 8 or below K, cap < 1, theta_ld < 1, LSE with lse_ld <
+ * N / 64 + 4, and with M, N > 0 a null A, W, cscale, theta, cnt, cand_i, or the epilogue's own cand_s /
+ * above / lse_part / mask. M == 0 or N == 0 is CLM_OK. clm_debug_set applies as to clm_gemm.
+ * clm_value_bounds: keys[0] / keys[1] (device) = the order key of min / max over v[0, n) (device), key(f)
+ * = bits(f) ^ 0xFFFFFFFF for a set sign bit, bits(f) | 0x80000000 otherwise; a NaN anywhere makes the
+ * decoded minimum (sign bit set) or maximum NaN. n == 0 gives {0xFFFFFFFF, 0}. CLM_E_ARG: n < 0, a null
+ * keys, a null v with n > 0. */
+enum { CLM_EPI_FILTER = 5, CLM_EPI_RANK = 6, CLM_EPI_LSE = 7, CLM_EPI_FILTER_MASK = 8 };
+int clm_gemm_select(int hip_device, int epilogue, int config, const void* A, int64_t lda, const void* W,
+                    int64_t ldw, int M, int N, int K, const float* rscale, const float* cscale,
+                    const float* theta, int64_t theta_ld, float margin, int* cnt, float* cand_s, int64_t* cand_i,
+                    int cap, int64_t base, const uint32_t* cbound, uint32_t* above, float* lse_part,
+                    int64_t lse_ld, float lse_c, const uint32_t* mask, int m_fastest, void* stream);
+int clm_value_bounds(int hip_device, const float* v, int64_t n, uint32_t* keys, void* stream);
 /* diagnostic flags (micro-benchmarks and tests only; 0 in production), initialised from
- * $CLM_GEMM_DEBUG: for later clm_gemm calls bit 0 = skip the epilogue (accumulators kept
+ * $CLM_GEMM_DEBUG: for later clm_gemm / clm_gemm_select calls bit 0 = skip the epilogue (accumulators kept
  * live), bit 1 = run the epilogue but drop every store, bit 2 = one tile per workgroup
  * instead of the persistent grid; for later encodes bit 3 (value 8) = run the last encoder
  * layer on every row instead of only the pooled rows, bit 4 (16) = q/k/v GEMM and attention
