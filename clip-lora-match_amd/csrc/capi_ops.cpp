@@ -146,6 +146,24 @@ int clm_collect_ge(int hip_device, const float* scores, int ldq, int nq, int64_t
   return CLM_OK;
 }
 
+int clm_topk_any(int hip_device, const float* scores, int64_t lds, const int64_t* idx, int64_t ldi, int64_t nq,
+                 int64_t C, int k, int64_t base, float* out_scores, int64_t* out_idx, void* stream) {
+  if (k < 1 || k > (1 << 26) || nq < 0 || nq > 65535 || C < 0 || C > 0xFFFFFFFFll || lds < C || (idx && ldi < C))
+    return fail(CLM_E_ARG, "bad topk_any shape (1 <= k <= 2^26, nq <= 65535, C <= 2^32 - 1, C <= lds, ldi)");
+  if (nq == 0) return CLM_OK;
+  if (!is_device_ptr(scores) || (idx && !is_device_ptr(idx)) || !is_device_ptr(out_scores) || !is_device_ptr(out_idx))
+    return fail(CLM_E_ARG, "topk_any: device pointers");
+  DeviceGuard g(hip_device);
+  hipStream_t st = (hipStream_t)stream;
+  Scratch& scr = scratch_of_current_device();
+  std::lock_guard<std::mutex> lock(scr.mu);
+  if (int rg = scratch_grow(scr, topk_any_ws_bytes(nq, k))) return rg;
+  KCHK(topk_any(scores, lds, idx, ldi, nq, C, k, base, out_scores, out_idx, k, scr.p, st));
+  HIPCHK(hipStreamSynchronize(st));   // the scratch is reused by the next call
+  scratch_trim(scr);
+  return CLM_OK;
+}
+
 int clm_topk_merge(int hip_device, const float* scores, const int64_t* idx, int64_t nq, int parts, int k_in, int k,
                    float* out_scores, int64_t* out_idx, void* stream) {
   if (nq < 0 || parts <= 0 || k_in <= 0 || k <= 0 || (int64_t)parts * k_in > 0x7FFFFFFF)

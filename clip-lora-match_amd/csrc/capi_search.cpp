@@ -931,15 +931,23 @@ static int masked_pass(clm_index* x, const QueryStage& qs, int64_t nq, int k, co
   return masked_redo(x, qs, k, words, redo, osc, oix, st);
 }
 
-static int search_masked(clm_index* x, const QueryStage& qs, int64_t nq, int k, const uint32_t* words,
-                         const uint32_t* bcnt, int64_t* boff, int flags, float* osc, int64_t* oix, hipStream_t st) {
-  const int64_t N = x->n, dim = x->dim;
+// The mask steps every filtered search starts with (clm_mask_rows runs them alone): the caller's words
+// prepared -- tail bits cleared, one count per block --, the blocks' offsets, and the total P brought
+// to the host (drains the stream).
+static int mask_plan(const uint32_t* src, int64_t N, uint32_t* words, uint32_t* bcnt, int64_t* boff, int64_t* P,
+                     hipStream_t st) {
   const int64_t nblk = mask_blocks(N);
-  int r;
+  KCHK(mask_prepare(src, N, words, bcnt, st));
   KCHK(mask_scan(bcnt, nblk, boff, st));
-  int64_t P = 0;
-  HIPCHK(hipMemcpyAsync(&P, boff + nblk, 8, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(P, boff + nblk, 8, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
+  return CLM_OK;
+}
+
+static int search_masked(clm_index* x, const QueryStage& qs, int64_t nq, int k, const uint32_t* words,
+                         const int64_t* boff, int64_t P, int flags, float* osc, int64_t* oix, hipStream_t st) {
+  const int64_t N = x->n, dim = x->dim;
+  int r;
   if (P == 0) {   // nothing is allowed: (-inf, -1) lists (counted with the exact route)
     x->search_stats[19] += nq;
     KCHK(fill_f32(osc, nq * k, -INFINITY, st));
@@ -1015,14 +1023,34 @@ int clm_index_search_masked(clm_index* x, const void* q, int q_dtype, int64_t nq
   }
   uint32_t* words = (uint32_t*)(qs.extra + o_words);
   uint32_t* bcnt = (uint32_t*)(qs.extra + o_bcnt);
-  KCHK(mask_prepare(src, N, words, bcnt, st));
-  r = search_masked(x, qs, nq, k, words, bcnt, (int64_t*)(qs.extra + o_boff), flags, osc, oix, st);
+  int64_t* boff = (int64_t*)(qs.extra + o_boff);
+  int64_t P = 0;
+  if ((r = mask_plan(src, N, words, bcnt, boff, &P, st))) return r;
+  r = search_masked(x, qs, nq, k, words, boff, P, flags, osc, oix, st);
   if (r) return r;
   if (!o_dev) {
     HIPCHK(copy_out(out_scores, osc, (size_t)nq * k * 4, st));
     HIPCHK(copy_out(out_idx, oix, (size_t)nq * k * 8, st));
   }
   HIPCHK(hipStreamSynchronize(st));   // workspaces are reused by the next call
+  return CLM_OK;
+}
+
+int clm_mask_rows(int hip_device, const uint32_t* allow, int64_t N, uint32_t* words, uint32_t* bcnt, int64_t* boff,
+                  uint32_t* list, int64_t* P_out, void* stream) {
+  if (N < 1 || N > 0xFFFFFFFFll) return fail(CLM_E_ARG, "mask_rows: 1 <= N <= 2^32 - 1");
+  if (!is_device_ptr(allow) || !is_device_ptr(words) || !is_device_ptr(bcnt) || !is_device_ptr(boff) ||
+      (list && !is_device_ptr(list)))
+    return fail(CLM_E_ARG, "mask_rows: device pointers");
+  DeviceGuard g(hip_device);
+  hipStream_t st = (hipStream_t)stream;
+  int64_t P = 0;
+  if (int r = mask_plan(allow, N, words, bcnt, boff, &P, st)) return r;
+  if (list && P > 0) {
+    KCHK(mask_compact(words, N, boff, list, st));
+    HIPCHK(hipStreamSynchronize(st));
+  }
+  if (P_out) *P_out = P;
   return CLM_OK;
 }
 

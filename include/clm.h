@@ -484,6 +484,24 @@ int64_t clm_scan16_waves(int hip_device, int64_t N, int dim);
  * [nq, cap] in no fixed order; cnt[q] (zeroed by the caller) counts them all, stored or not. */
 int clm_collect_ge(int hip_device, const float* scores, int ldq, int nq, int64_t C, const float* th, int* cnt, int cap,
                    float* cand_s, int64_t* cand_i, int64_t base, void* stream);
+/* clm_topk_any: the top-k of any k (the search's path for k > 1024 and the merge's past one LDS sort), test
+ * hook, device pointers. Row q of scores [nq, lds >= C] f32; idx (or NULL) [nq, ldi >= C]: an entry with
+ * idx < 0 cannot be taken. out_scores / out_idx [nq, k]: the first k takeable entries by (order key of the
+ * score desc -- key as clm_value_bounds: a positive NaN above +inf, a negative one below -inf, +0 above -0
+ * --, low 32 bits of idx, or the column, asc), then (-inf, -1). The id is idx's value (below 2^32; base is
+ * ignored), or base + column without idx. The workspace is the device scratch; the call drains the stream.
+ * CLM_E_ARG, nothing written: k < 1, nq < 0 or > 65535, C < 0 or > 2^32 - 1, lds < C, ldi < C with idx, a
+ * pointer that is not device memory. nq == 0 is CLM_OK. */
+int clm_topk_any(int hip_device, const float* scores, int64_t lds, const int64_t* idx, int64_t ldi, int64_t nq,
+                 int64_t C, int k, int64_t base, float* out_scores, int64_t* out_idx, void* stream);
+/* clm_mask_rows: the mask steps of clm_index_search_masked, in its order (test hook, device pointers):
+ * words [ceil(N / 32)] = allow's words with the bits at or past N cleared (allow is not written), bcnt
+ * [blocks] = the set bits of each block of 8192 rows (blocks = ceil(N / 8192)), boff [blocks + 1] = their
+ * exclusive prefix sums, boff[blocks] = P, list (or NULL: not built) [>= P, the caller's to size: N always
+ * holds it] = the set rows ascending; *P_out (a host int64, or NULL) = P. The call drains the stream.
+ * CLM_E_ARG, nothing written: N < 1 or > 2^32 - 1, a pointer that is not device memory. */
+int clm_mask_rows(int hip_device, const uint32_t* allow, int64_t N, uint32_t* words, uint32_t* bcnt, int64_t* boff,
+                  uint32_t* list, int64_t* P_out, void* stream);
 /* attention over qkv [B*T, 3*H*64] (q pre-scaled by 64^-1/2), out [B*T, ldo] (device
  * pointers); causal: 0 / non-0 switch (the text tower's mask). */
 int clm_attention(int hip_device, int dtype, int causal, const void* qkv, void* out, int64_t ldo,
