@@ -881,7 +881,7 @@ int clm_gemm_select(int hip_device, int epilogue, int config, const void* A, int
                     int64_t theta_ld, float margin, int* cnt, float* cand_s, int64_t* cand_i, int cap, int64_t base,
                     const uint32_t* cbound, uint32_t* above, float* lse_part, int64_t lse_ld, float lse_c,
                     const uint32_t* mask, int m_fastest, void* stream) {
-  if (epilogue != EPI_FILTER && epilogue != EPI_RANK && epilogue != EPI_LSE && epilogue != EPI_FILTER_MASK)
+  if (!epi_selects(epilogue))
     return fail(CLM_E_ARG, "gemm_select: epilogue must be FILTER, RANK, LSE or FILTER_MASK");
   if (config >= gemm_num_configs()) return fail(CLM_E_ARG, "bad config");
   if (M < 0 || N < 0 || K <= 0 || K % 64 || lda % 8 || ldw % 8 || lda < K || ldw < K)

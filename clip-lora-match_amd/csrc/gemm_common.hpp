@@ -54,17 +54,75 @@ __device__ __forceinline__ void lds_barrier() {
   asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
 
+// The selecting epilogues (epi_selects: FILTER / FILTER_MASK / RANK / LSE), the part the vector
+// loop of epilogue() and the ragged-N path share: one row's edges and per-lane totals, the decision
+// on one score, and the row's finish. th = the row's theta: FILTER / FILTER_MASK's threshold,
+// RANK's target score t, LSE's head floor.
+struct SelectRow {
+  int m;
+  float th, lo, hi;   // lo: the lower edge of what is listed; hi (RANK): above it a score is counted
+  unsigned up;        // RANK: this lane's scores above hi
+  float sum;          // LSE: this lane's tail terms
+};
+template <int EPI>
+__device__ __forceinline__ SelectRow select_row(const GemmArgs& g, int m, float th) {
+  constexpr bool BAND = EPI == EPI_RANK || EPI == EPI_LSE;   // they list a band of undecided rows from theta - margin up
+  return SelectRow{m, th, BAND ? th - g.rank_margin : th, th + g.rank_margin, 0u, 0.f};
+}
+// Score sc of column n, whose mask bit is `open` (FILTER_MASK; a closed column is not tested).
+// At or above lo it takes a slot of the row's list from cnt (counted past cap, stored below it):
+// FILTER / FILTER_MASK store the score and the id, RANK / LSE the id alone. RANK counts a score
+// above hi instead (certainly ahead of the target) and drops one below lo; LSE adds one below lo to
+// the tail as exp2((s - theta) * c), c = scale * log2(e), a term below 1: no running maximum. A NaN
+// score fails every comparison: dropped, and in LSE it makes the tail NaN.
+template <int EPI>
+__device__ __forceinline__ void select_one(const GemmArgs& g, SelectRow& r, int n, bool open, float sc) {
+  if (EPI == EPI_FILTER_MASK && !open) return;
+  if (EPI == EPI_RANK && sc > r.hi) {
+    ++r.up;
+  } else if (sc >= r.lo) {
+    const int slot = atomicAdd(g.cnt + r.m, 1);
+    if (slot < g.cap) {
+      if constexpr (EPI == EPI_FILTER || EPI == EPI_FILTER_MASK) g.cand_s[(int64_t)r.m * g.cap + slot] = sc;
+      g.cand_i[(int64_t)r.m * g.cap + slot] = g.base + n;
+    }
+  } else if (EPI == EPI_LSE) {
+    r.sum += __builtin_amdgcn_exp2f((sc - r.th) * g.lse_c);
+  }
+}
+// The row's totals are summed over the 4 lanes l, l ^ 16, l ^ 32, l ^ 48 that hold it (all of them
+// must be here: m depends on lane & 15 only) and lane l < 16 writes them. RANK: one integer
+// atomicAdd per row and wave -- the total does not depend on the order. LSE: the wave's partial of
+// this column tile goes to its own slot (column tile, wave column) of the row's slab: every slot of
+// a live row is written exactly once per pass, in no atomic, so lse_reduce's fixed-order sum is
+// reproducible.
+template <int EPI>
+__device__ __forceinline__ void select_finish(const GemmArgs& g, const SelectRow& r, bool live, int lane, int slot) {
+  if constexpr (EPI == EPI_RANK) {
+    unsigned up = r.up;
+    up += (unsigned)__shfl_xor((int)up, 16, 64);
+    up += (unsigned)__shfl_xor((int)up, 32, 64);
+    if (lane < 16 && live && up) atomicAdd(g.above + r.m, up);
+  } else if constexpr (EPI == EPI_LSE) {
+    float sum = r.sum;
+    sum += __shfl_xor(sum, 16, 64);
+    sum += __shfl_xor(sum, 32, 64);
+    if (lane < 16 && live) g.lse_part[(int64_t)r.m * g.lse_ld + slot] = sum;
+  }
+}
+
 // ragged-N epilogue (N or ldo not a multiple of 4): element by element, same arithmetic
-// as the vector paths (score = dot * rscale * cscale in that order)
+// as the vector paths (score = dot * rscale * cscale in that order; the selecting epilogues
+// through select_one / select_finish, lse_slot = the wave's slab slot)
 template <bool BF, int EPI, int TM, int TN>
 __device__ __forceinline__ void epilogue_scalar(const GemmArgs& g, const f32x4 (&acc)[TM][TN], int wrow, int wcol,
-                                                int lse_slot = 0) {
+                                                int lse_slot) {
 #pragma unroll
   for (int mb = 0; mb < TM; ++mb) {
     const int m = wrow + mb * 16;
     if (m >= g.M) continue;
-    const float rs = (EPI == EPI_SCORE || EPI == EPI_FILTER || EPI == EPI_RANK || EPI == EPI_LSE || EPI == EPI_FILTER_MASK) && g.rscale ? g.rscale[m] : 1.f;
-    float lse_sum = 0.f;   // EPI_LSE: this lane's tail terms of row m
+    const float rs = (EPI == EPI_SCORE || epi_selects(EPI)) && g.rscale ? g.rscale[m] : 1.f;
+    SelectRow sel = select_row<EPI>(g, m, epi_selects(EPI) ? g.theta[(int64_t)m * g.theta_ld] : 0.f);
     int64_t prow = m;
     const float* aux = nullptr;
     if constexpr (EPI == EPI_PATCH) {
@@ -90,55 +148,22 @@ __device__ __forceinline__ void epilogue_scalar(const GemmArgs& g, const f32x4 (
           if (g.out16) ((u16*)g.out)[(int64_t)m * g.ldo + nj] = (u16)f16_down(v);
           else ((float*)g.out)[(int64_t)m * g.ldo + nj] = v;
         }
-        else if constexpr (EPI == EPI_RANK) {
-          const float sc = x * rs * g.cscale[nj];
-          const float t = g.theta[(int64_t)m * g.theta_ld];
-          if (sc > t + g.rank_margin) {
-            atomicAdd(g.above + m, 1u);
-          } else if (sc >= t - g.rank_margin) {
-            const int slot = atomicAdd(g.cnt + m, 1);
-            if (slot < g.cap) g.cand_i[(int64_t)m * g.cap + slot] = g.base + nj;
-          }
-        }
-        else if constexpr (EPI == EPI_LSE) {   // the vector path's arithmetic, element by element
-          const float sc = x * rs * g.cscale[nj];
-          const float t = g.theta[(int64_t)m * g.theta_ld];
-          if (sc >= t - g.rank_margin) {
-            const int slot = atomicAdd(g.cnt + m, 1);
-            if (slot < g.cap) g.cand_i[(int64_t)m * g.cap + slot] = g.base + nj;
-          } else {
-            lse_sum += __builtin_amdgcn_exp2f((sc - t) * g.lse_c);
-          }
-        }
-        else if constexpr (EPI == EPI_FILTER_MASK) {   // FILTER over the allowed rows (the vector path's test)
-          if (!((g.mask[nj >> 5] >> (nj & 31)) & 1u)) continue;
-          const float sc = x * rs * g.cscale[nj];
-          if (sc >= g.theta[(int64_t)m * g.theta_ld]) {
-            const int slot = atomicAdd(g.cnt + m, 1);
-            if (slot < g.cap) {
-              g.cand_s[(int64_t)m * g.cap + slot] = sc;
-              g.cand_i[(int64_t)m * g.cap + slot] = g.base + nj;
-            }
-          }
-        }
         else {
-          const float sc = x * rs * g.cscale[nj];
-          if (sc >= g.theta[(int64_t)m * g.theta_ld]) {
-            const int slot = atomicAdd(g.cnt + m, 1);
-            if (slot < g.cap) {
-              g.cand_s[(int64_t)m * g.cap + slot] = sc;
-              g.cand_i[(int64_t)m * g.cap + slot] = g.base + nj;
-            }
-          }
+          static_assert(epi_selects(EPI), "unknown epilogue");
+          const bool open = EPI != EPI_FILTER_MASK || ((g.mask[nj >> 5] >> (nj & 31)) & 1u);
+          select_one<EPI>(g, sel, nj, open, x * rs * g.cscale[nj]);
         }
       }
     }
-    if constexpr (EPI == EPI_LSE) {   // the 4 lanes of row m are all live here (m depends on lane & 15 only)
-      lse_sum += __shfl_xor(lse_sum, 16, 64);
-      lse_sum += __shfl_xor(lse_sum, 32, 64);
-      if ((threadIdx.x & 63) < 16) g.lse_part[(int64_t)m * g.lse_ld + lse_slot] = lse_sum;
-    }
+    select_finish<EPI>(g, sel, true, threadIdx.x & 63, lse_slot);
   }
+  // A lane whose columns all lie past N never uses the row values it loaded. The compiler does not
+  // see the main loops' counted waits (inline asm), so in a persistent kernel it would carry those
+  // loads around the tile loop as still in flight and wait wherever it reuses their registers --
+  // on the vector path between the batched row loads, one memory round trip per load (measured:
+  // 3 % of the benchmark's filter pass). A wait it does see, here where time does not matter,
+  // leaves nothing in flight.
+  if constexpr (epi_selects(EPI)) __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0)
 }
 
 // Residual prefetch (EPI_RESID in gemm_kernel): the fp32 residual values of the first P row-blocks
@@ -180,8 +205,7 @@ __device__ __forceinline__ void epilogue(const GemmArgs& g, const f32x4 (&acc)[B
   const int wrow = m0 + wm * (BM / WM) + (lane & 15);
   const int wcol = n0 + wn * (BN / WN) + (lane >> 4) * 4;
   if ((g.N % 4) != 0 || (g.ldo % 4) != 0) {   // ragged N: scalar tail path
-    if constexpr (EPI == EPI_LSE) epilogue_scalar<BF, EPI, C::TM, C::TN>(g, acc, wrow, wcol, (n0 / BN) * WN + wn);
-    else epilogue_scalar<BF, EPI, C::TM, C::TN>(g, acc, wrow, wcol);
+    epilogue_scalar<BF, EPI, C::TM, C::TN>(g, acc, wrow, wcol, (n0 / BN) * WN + wn);
     return;
   }
   // per-column vectors, loaded once per nb (they do not depend on the row); the RESID/PATCH
@@ -191,9 +215,9 @@ __device__ __forceinline__ void epilogue(const GemmArgs& g, const f32x4 (&acc)[B
   float4 cv[C::TN];
 #pragma unroll
   for (int nb = 0; nb < C::TN; ++nb) {
-    if constexpr (!HOIST || EPI == EPI_FILTER || EPI == EPI_RANK || EPI == EPI_LSE || EPI == EPI_FILTER_MASK) break;   // FILTER / RANK: loaded after the skip test; LSE: per block
+    if constexpr (!HOIST || epi_selects(EPI)) break;   // selecting: loaded per block, after the skip test
     const int n = wcol + nb * 16;
-    if constexpr (EPI == EPI_SCORE || EPI == EPI_FILTER)
+    if constexpr (EPI == EPI_SCORE)
       cv[nb] = (g.cscale && n < g.N) ? *(const float4*)(g.cscale + n) : make_float4(1.f, 1.f, 1.f, 1.f);
     else
       cv[nb] = (g.bias && n < g.N) ? *(const float4*)(g.bias + n) : make_float4(0.f, 0.f, 0.f, 0.f);
@@ -318,166 +342,77 @@ __device__ __forceinline__ void epilogue(const GemmArgs& g, const f32x4 (&acc)[B
         }
       }
     }
-  } else {   // EPI_SCORE / EPI_FILTER / EPI_RANK / EPI_LSE: score = dot * rscale[m] * cscale[n], in this order
+  } else {   // EPI_SCORE and the selecting epilogues: score = dot * rscale[m] * cscale[n], in this order
     float rs[C::TM], th[C::TM];
 #pragma unroll
     for (int mb = 0; mb < C::TM; ++mb) {
       const int m = wrow + mb * 16;
       rs[mb] = (g.rscale && m < g.M) ? g.rscale[m] : 1.f;
-      if constexpr (EPI == EPI_FILTER || EPI == EPI_RANK || EPI == EPI_LSE || EPI == EPI_FILTER_MASK) th[mb] = m < g.M ? g.theta[(int64_t)m * g.theta_ld] : 0.f;
+      if constexpr (epi_selects(EPI)) th[mb] = m < g.M ? g.theta[(int64_t)m * g.theta_ld] : 0.f;
     }
-    if constexpr (EPI == EPI_LSE) {
-      // Log-sum-exp epilogue: th = the row's head floor theta. A score at or above theta - margin
-      // is a band row (its index appended to the row's band list, FILTER's slot scheme; the band
-      // kernel re-scores it exactly); every other row is a tail row and adds
-      // exp2((s - theta) * c), c = scale * log2(e), a term below 1: no running maximum. A NaN score
-      // fails the band test and makes the tail NaN. No skip test: every row contributes. The
-      // terms are summed per lane, then over the 4 lanes l, l ^ 16, l ^ 32, l ^ 48 that hold the
-      // row, and lane l < 16 stores the wave's partial of this column tile to its own slot
-      // (column tile, wave column) of the row's slab: every slot of a live row is written exactly
-      // once per pass, in no atomic, so lse_reduce's fixed-order sum is reproducible.
-      const int slot = (n0 / BN) * WN + wn;
-#pragma unroll
-      for (int mb = 0; mb < C::TM; ++mb) {
-        const int m = wrow + mb * 16;
-        const bool live = m < g.M;
-        const float lo = th[mb] - g.rank_margin;
-        float sum = 0.f;
-#pragma unroll
-        for (int nb = 0; nb < C::TN; ++nb) {
-          const int n = wcol + nb * 16;
-          if (!live || n >= g.N) continue;
-          const float4 c = g.cscale ? *(const float4*)(g.cscale + n) : make_float4(1.f, 1.f, 1.f, 1.f);
-          const float sc[4] = {acc[mb][nb][0] * rs[mb] * c.x, acc[mb][nb][1] * rs[mb] * c.y,
-                               acc[mb][nb][2] * rs[mb] * c.z, acc[mb][nb][3] * rs[mb] * c.w};
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            if (sc[j] >= lo) {
-              const int sl = atomicAdd(g.cnt + m, 1);
-              if (sl < g.cap) g.cand_i[(int64_t)m * g.cap + sl] = g.base + n + j;
-            } else {
-              sum += __builtin_amdgcn_exp2f((sc[j] - th[mb]) * g.lse_c);
-            }
-          }
-        }
-        sum += __shfl_xor(sum, 16, 64);
-        sum += __shfl_xor(sum, 32, 64);
-        if (lane < 16 && live) g.lse_part[(int64_t)m * g.lse_ld + slot] = sum;
-      }
-      return;
-    }
-    if constexpr (EPI == EPI_RANK) {
-      // Counting epilogue: th = the row's target score t. A score above t + margin is certainly
-      // ahead of the target (counted: per lane, summed over the 4 lanes l, l ^ 16, l ^ 32, l ^ 48
-      // that hold the row, one integer atomicAdd per row and wave -- the total does not depend on
-      // the order); one inside [t - margin, t + margin] is undecided (its index appended to the
-      // row's band list, FILTER's slot scheme); one below is dropped. FILTER's skip test with the
-      // band's lower edge as the threshold: a row block / block whose largest possible score is
-      // below it holds nothing to count or append.
-      float cmin = 0.f, cmax = 0.f;
-      bool cok = false;
-      if (g.cbound) {
-        cmin = key_float(g.cbound[0]);
-        cmax = key_float(g.cbound[1]);
-        cok = cmin >= 0.f && cmax <= 3.4028235e38f;   // NaN fails both
-      }
-#pragma unroll
-      for (int mb = 0; mb < C::TM; ++mb) {
-        const int m = wrow + mb * 16;
-        const bool live = m < g.M;
-        const float lo = th[mb] - g.rank_margin, hi = th[mb] + g.rank_margin;
-        const bool rok = cok && rs[mb] >= 0.f && rs[mb] <= 3.4028235e38f && lo >= -3.4028235e38f;
-        float bmx[C::TN];
-        float mx = -3.4028235e38f;
-#pragma unroll
-        for (int nb = 0; nb < C::TN; ++nb) {
-          bmx[nb] = fmaxf(fmaxf(acc[mb][nb][0], acc[mb][nb][1]), fmaxf(acc[mb][nb][2], acc[mb][nb][3]));
-          mx = fmaxf(mx, bmx[nb]);
-        }
-        auto reach = [&](float v) { return live && (!rok || (v * rs[mb]) * (v >= 0.f ? cmax : cmin) >= lo); };
-        if (!__any(reach(mx))) continue;
-        unsigned up = 0;
-#pragma unroll
-        for (int nb = 0; nb < C::TN; ++nb) {
-          if (!__any(reach(bmx[nb]))) continue;
-          const int n = wcol + nb * 16;
-          if (!live || n >= g.N) continue;
-          const float4 c = g.cscale ? *(const float4*)(g.cscale + n) : make_float4(1.f, 1.f, 1.f, 1.f);
-          const float sc[4] = {acc[mb][nb][0] * rs[mb] * c.x, acc[mb][nb][1] * rs[mb] * c.y,
-                               acc[mb][nb][2] * rs[mb] * c.z, acc[mb][nb][3] * rs[mb] * c.w};
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            if (sc[j] > hi) {
-              ++up;
-            } else if (sc[j] >= lo) {
-              const int slot = atomicAdd(g.cnt + m, 1);
-              if (slot < g.cap) g.cand_i[(int64_t)m * g.cap + slot] = g.base + n + j;
-            }
-          }
-        }
-        up += (unsigned)__shfl_xor((int)up, 16, 64);
-        up += (unsigned)__shfl_xor((int)up, 32, 64);
-        if (lane < 16 && live && up) atomicAdd(g.above + m, up);
-      }
-      return;
-    }
-    if constexpr (EPI == EPI_FILTER_MASK) {
-      // FILTER over the rows a bitset allows. The lane's 4 columns n .. n + 3 (n % 4 == 0) are one
-      // nibble of word n >> 5, which never straddles a word; the nibbles do not depend on the row
-      // block, so they are read once per tile (the words of a tile: BN / 8 bytes, L2-resident).
-      // FILTER's skip test with the mask folded in: a lane without a set bit in a block cannot
-      // append from it, so a block no lane of the wave can append from -- by its bits or by its
-      // largest possible score -- is skipped before its cscale load. Appends are exactly FILTER's
-      // for the columns whose bit is set (same arithmetic, same slot scheme).
-      unsigned nib[C::TN];
-      unsigned any_bits = 0;
+    if constexpr (epi_selects(EPI)) {
+      // One loop over the row blocks and their 16 x 16 blocks for FILTER / FILTER_MASK / RANK / LSE.
+      // What differs between them is compile-time: the lower edge and what a score does on either
+      // side of it (select_row / select_one), the row's finish (select_finish), FILTER_MASK's bits
+      // and whether there is a skip test. LSE has none: every row contributes to its tail sum.
+      constexpr bool MASKED = EPI == EPI_FILTER_MASK, SKIP = EPI != EPI_LSE;
+      // FILTER_MASK: the lane's 4 columns n .. n + 3 (n % 4 == 0) are one nibble of word n >> 5,
+      // which never straddles a word; the nibbles do not depend on the row block, so they are read
+      // once per tile (the words of a tile: BN / 8 bytes, L2-resident). The others: all four open.
+      unsigned nib[C::TN], any_bits = 0;
 #pragma unroll
       for (int nb = 0; nb < C::TN; ++nb) {
         const int n = wcol + nb * 16;
-        nib[nb] = n < g.N ? (g.mask[n >> 5] >> (n & 31)) & 15u : 0u;
+        nib[nb] = !MASKED ? 15u : n < g.N ? (g.mask[n >> 5] >> (n & 31)) & 15u : 0u;
         any_bits |= nib[nb];
       }
-      if (!__any(any_bits != 0)) return;
+      if (MASKED && !__any(any_bits != 0)) return;
+      // Skip test: with cmin = min cscale >= 0 and cmax = max cscale finite, every score of a
+      // 16 x 16 block, (acc * rs) * c, is at most (mx * rs) * (mx >= 0 ? cmax : cmin), mx = the
+      // block's largest accumulator on the lane (fp32 multiplication is monotonic; same operation
+      // order as the scores), so a row block / block whose largest possible score is below the
+      // row's lower edge on every lane of the wave holds nothing to append or count, and is skipped
+      // whole, before its cscale loads. Out-of-range columns (clamped operand rows) only raise mx.
+      // FILTER_MASK folds its bits in: a lane without a set bit in a block cannot append from it.
+      // Without cbound, or with scales or an edge the bound does not hold for, nothing is skipped.
+      // The appended (score, row) set and the count are exactly the unskipped ones.
       float cmin = 0.f, cmax = 0.f;
       bool cok = false;
-      if (g.cbound) {
+      if (SKIP && g.cbound) {
         cmin = key_float(g.cbound[0]);
         cmax = key_float(g.cbound[1]);
         cok = cmin >= 0.f && cmax <= 3.4028235e38f;   // NaN fails both
       }
+      const int slot = (n0 / BN) * WN + wn;   // LSE: the wave's slab slot
 #pragma unroll
       for (int mb = 0; mb < C::TM; ++mb) {
-        const int m = wrow + mb * 16;
-        const bool live = m < g.M;
-        const bool rok = cok && rs[mb] >= 0.f && rs[mb] <= 3.4028235e38f && th[mb] >= -3.4028235e38f;
+        SelectRow r = select_row<EPI>(g, wrow + mb * 16, th[mb]);
+        const bool live = r.m < g.M;
+        const bool rok = cok && rs[mb] >= 0.f && rs[mb] <= 3.4028235e38f && r.lo >= -3.4028235e38f;
+        auto reach = [&](float v) { return live && (!rok || (v * rs[mb]) * (v >= 0.f ? cmax : cmin) >= r.lo); };
         float bmx[C::TN];
-        float mx = -3.4028235e38f;
+        if constexpr (SKIP) {
+          float mx = -3.4028235e38f;
 #pragma unroll
-        for (int nb = 0; nb < C::TN; ++nb) {
-          bmx[nb] = fmaxf(fmaxf(acc[mb][nb][0], acc[mb][nb][1]), fmaxf(acc[mb][nb][2], acc[mb][nb][3]));
-          if (nib[nb]) mx = fmaxf(mx, bmx[nb]);
+          for (int nb = 0; nb < C::TN; ++nb) {
+            bmx[nb] = fmaxf(fmaxf(acc[mb][nb][0], acc[mb][nb][1]), fmaxf(acc[mb][nb][2], acc[mb][nb][3]));
+            if (nib[nb]) mx = fmaxf(mx, bmx[nb]);
+          }
+          if (!__any(any_bits != 0 && reach(mx))) continue;
         }
-        auto reach = [&](float v) { return live && (!rok || (v * rs[mb]) * (v >= 0.f ? cmax : cmin) >= th[mb]); };
-        if (!__any(any_bits != 0 && reach(mx))) continue;
 #pragma unroll
         for (int nb = 0; nb < C::TN; ++nb) {
-          if (!__any(nib[nb] != 0 && reach(bmx[nb]))) continue;
+          if constexpr (SKIP)
+            if (!__any(nib[nb] != 0 && reach(bmx[nb]))) continue;
           const int n = wcol + nb * 16;
-          if (!live || !nib[nb]) continue;   // a set bit implies n < N
+          if (!live || (MASKED ? !nib[nb] : n >= g.N)) continue;   // a set bit implies n < N
           const float4 c = g.cscale ? *(const float4*)(g.cscale + n) : make_float4(1.f, 1.f, 1.f, 1.f);
           const float sc[4] = {acc[mb][nb][0] * rs[mb] * c.x, acc[mb][nb][1] * rs[mb] * c.y,
                                acc[mb][nb][2] * rs[mb] * c.z, acc[mb][nb][3] * rs[mb] * c.w};
 #pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            if (((nib[nb] >> j) & 1u) && sc[j] >= th[mb]) {
-              const int slot = atomicAdd(g.cnt + m, 1);
-              if (slot < g.cap) {
-                g.cand_s[(int64_t)m * g.cap + slot] = sc[j];
-                g.cand_i[(int64_t)m * g.cap + slot] = g.base + n + j;
-              }
-            }
-          }
+          for (int j = 0; j < 4; ++j) select_one<EPI>(g, r, n + j, (nib[nb] >> j) & 1u, sc[j]);
         }
+        select_finish<EPI>(g, r, live, lane, slot);
       }
       return;
     }
@@ -547,92 +482,18 @@ __device__ __forceinline__ void epilogue(const GemmArgs& g, const f32x4 (&acc)[B
               ob, off, 0, 0);
         }
       }
-    } else {
-      // Skip test: with cmin = min cscale >= 0 and cmax = max cscale finite, every score of a
-      // 16 x 16 block, (acc * rs) * c, is at most (mx * rs) * (mx >= 0 ? cmax : cmin), mx = the
-      // block's largest accumulator on the lane (fp32 multiplication is monotonic; same operation
-      // order as the scores), so a row block / block that no lane of the wave can append from is
-      // skipped whole, before its cscale loads. Out-of-range columns (clamped operand rows) only
-      // raise mx. The appended (score, row) set is exactly the unskipped path's.
-      if (g.cbound) {
-        const float cmin = key_float(g.cbound[0]), cmax = key_float(g.cbound[1]);
-        const bool cok = cmin >= 0.f && cmax <= 3.4028235e38f;   // NaN fails both
-#pragma unroll
-        for (int mb = 0; mb < C::TM; ++mb) {
-          const int m = wrow + mb * 16;
-          const bool live = m < g.M;
-          const bool rok = cok && rs[mb] >= 0.f && rs[mb] <= 3.4028235e38f && th[mb] >= -3.4028235e38f;
-          float bmx[C::TN];
-          float mx = -3.4028235e38f;
-#pragma unroll
-          for (int nb = 0; nb < C::TN; ++nb) {
-            bmx[nb] = fmaxf(fmaxf(acc[mb][nb][0], acc[mb][nb][1]), fmaxf(acc[mb][nb][2], acc[mb][nb][3]));
-            mx = fmaxf(mx, bmx[nb]);
-          }
-          auto reach = [&](float v) { return live && (!rok || (v * rs[mb]) * (v >= 0.f ? cmax : cmin) >= th[mb]); };
-          if (!__any(reach(mx))) continue;
-#pragma unroll
-          for (int nb = 0; nb < C::TN; ++nb) {
-            if (!__any(reach(bmx[nb]))) continue;
-            const int n = wcol + nb * 16;
-            if (!live || n >= g.N) continue;
-            const float4 c = g.cscale ? *(const float4*)(g.cscale + n) : make_float4(1.f, 1.f, 1.f, 1.f);
-            const float sc[4] = {acc[mb][nb][0] * rs[mb] * c.x, acc[mb][nb][1] * rs[mb] * c.y,
-                                 acc[mb][nb][2] * rs[mb] * c.z, acc[mb][nb][3] * rs[mb] * c.w};
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-              if (sc[j] >= th[mb]) {
-                const int slot = atomicAdd(g.cnt + m, 1);
-                if (slot < g.cap) {
-                  g.cand_s[(int64_t)m * g.cap + slot] = sc[j];
-                  g.cand_i[(int64_t)m * g.cap + slot] = g.base + n + j;
-                }
-              }
-            }
-          }
-        }
-        return;
-      }
-#pragma unroll
-      for (int nb = 0; nb < C::TN; ++nb) {
-        const int n = wcol + nb * 16;
-        cv[nb] = (g.cscale && n < g.N) ? *(const float4*)(g.cscale + n) : make_float4(1.f, 1.f, 1.f, 1.f);
-      }
-#pragma unroll
-      for (int mb = 0; mb < C::TM; ++mb) {
-        const int m = wrow + mb * 16;
-        if (m >= g.M) continue;
-#pragma unroll
-        for (int nb = 0; nb < C::TN; ++nb) {
-          const int n = wcol + nb * 16;
-          if (n >= g.N) continue;
-          const float4 c = cv[nb];
-          const float sc[4] = {acc[mb][nb][0] * rs[mb] * c.x, acc[mb][nb][1] * rs[mb] * c.y,
-                               acc[mb][nb][2] * rs[mb] * c.z, acc[mb][nb][3] * rs[mb] * c.w};
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            if (sc[j] >= th[mb]) {
-              const int slot = atomicAdd(g.cnt + m, 1);
-              if (slot < g.cap) {
-                g.cand_s[(int64_t)m * g.cap + slot] = sc[j];
-                g.cand_i[(int64_t)m * g.cap + slot] = g.base + n + j;
-              }
-            }
-          }
-        }
-      }
     }
   }
 }
 
 // Stores (vector-memory instructions) one tile's epilogue issues per wave at least, on the
 // vector paths; the main loop's counted vmcnt leaves this many in flight after a tile end
-// (a smaller count than actually issued only over-waits). FILTER / RANK / LSE store in branches: 0.
+// (a smaller count than actually issued only over-waits). The selecting epilogues store in branches: 0.
 // EPI_SCORE with TN == 8 may run the group-maxima form (GemmArgs::out16 == 2: one 16-B store per
 // row-block, TM in all), so it counts TM.
 template <int EPI, int TM, int TN>
 constexpr int epi_min_stores() {
-  return epi_stores16(EPI) ? TM * TN / 2 : (EPI == EPI_FILTER || EPI == EPI_RANK || EPI == EPI_LSE || EPI == EPI_FILTER_MASK) ? 0 : (EPI == EPI_SCORE && TN == 8) ? TM : TM * TN;
+  return epi_stores16(EPI) ? TM * TN / 2 : epi_selects(EPI) ? 0 : (EPI == EPI_SCORE && TN == 8) ? TM : TM * TN;
 }
 
 }  // namespace gemm_detail

@@ -335,7 +335,7 @@ int pick_config(int epi, int M, int N) {
     forced = e ? atoi(e) : -1;
   }
   // the rank pass exists on the filter's tiles only (config 1 and G2's 8-11)
-  if (epi == EPI_RANK || epi == EPI_LSE || epi == EPI_FILTER_MASK) return (forced == 1 || (forced >= 8 && forced <= 11)) ? forced : pick_from(MODELS_G2, M, N);
+  if (epi_selects(epi) && epi != EPI_FILTER) return (forced == 1 || (forced >= 8 && forced <= 11)) ? forced : pick_from(MODELS_G2, M, N);
   if (forced >= 0 && forced < NCFG) return forced;
   // the search's filter GEMM (K = 512, no stores): G2's loop, 256 x 192 -- configs[4] search
   // 95.9 k QPS vs 86.4 k with gemm_kernel 256 x 256 (profiles/r04_v7_search_cfg_ab.txt)
@@ -353,6 +353,18 @@ int pick_config(int epi, int M, int N) {
   return pick_from(MODELS_G2, M, N);
 }
 
+// RANK / LSE / FILTER_MASK: fp16, on the tiles the filter pass runs on (config 1 and G2's 8-11);
+// FILTER_MASK requires the mask words
+template <bool BF, int EPI>
+hipError_t launch_fp16_select(int id, const GemmArgs& g, hipStream_t s) {
+  if constexpr (!BF) {
+    if (EPI == EPI_FILTER_MASK && !g.mask) return hipErrorInvalidValue;
+    if (id == 1) return launch_cfg<false, EPI, 256, 256, 4, 2, 2>(g, s);
+    if (id >= 8 && id <= 11) return gemm2_launch(false, EPI, id, g, s);
+  }
+  return hipErrorInvalidValue;
+}
+
 template <bool BF>
 hipError_t dispatch(int epi, int id, const GemmArgs& g, hipStream_t s) {
   switch (epi) {
@@ -362,25 +374,9 @@ hipError_t dispatch(int epi, int id, const GemmArgs& g, hipStream_t s) {
     case EPI_PATCH: return launch_id<BF, EPI_PATCH>(id, g, s);
     case EPI_SCORE: return launch_id<BF, EPI_SCORE>(id, g, s);
     case EPI_FILTER: return launch_id<BF, EPI_FILTER>(id, g, s);
-    case EPI_RANK:   // fp16, on the tiles the filter pass runs on
-      if constexpr (!BF) {
-        if (id == 1) return launch_cfg<false, EPI_RANK, 256, 256, 4, 2, 2>(g, s);
-        if (id >= 8 && id <= 11) return gemm2_launch(false, EPI_RANK, id, g, s);
-      }
-      return hipErrorInvalidValue;
-    case EPI_LSE:   // as EPI_RANK
-      if constexpr (!BF) {
-        if (id == 1) return launch_cfg<false, EPI_LSE, 256, 256, 4, 2, 2>(g, s);
-        if (id >= 8 && id <= 11) return gemm2_launch(false, EPI_LSE, id, g, s);
-      }
-      return hipErrorInvalidValue;
-    case EPI_FILTER_MASK:   // as EPI_RANK; the mask words are required
-      if constexpr (!BF) {
-        if (!g.mask) return hipErrorInvalidValue;
-        if (id == 1) return launch_cfg<false, EPI_FILTER_MASK, 256, 256, 4, 2, 2>(g, s);
-        if (id >= 8 && id <= 11) return gemm2_launch(false, EPI_FILTER_MASK, id, g, s);
-      }
-      return hipErrorInvalidValue;
+    case EPI_RANK: return launch_fp16_select<BF, EPI_RANK>(id, g, s);
+    case EPI_LSE: return launch_fp16_select<BF, EPI_LSE>(id, g, s);
+    case EPI_FILTER_MASK: return launch_fp16_select<BF, EPI_FILTER_MASK>(id, g, s);
     default: return hipErrorInvalidValue;
   }
 }

@@ -218,6 +218,11 @@ hipError_t by_id(int id, const GemmArgs& g, hipStream_t s) {
     default: return hipErrorInvalidValue;
   }
 }
+template <bool BF, int EPI>   // the epilogues that exist in fp16 only
+hipError_t by_id_fp16(int id, const GemmArgs& g, hipStream_t s) {
+  if constexpr (!BF) return by_id<false, EPI>(id, g, s);
+  return hipErrorInvalidValue;
+}
 template <bool BF>
 hipError_t by_epi(int epi, int id, const GemmArgs& g, hipStream_t s) {
   switch (epi) {
@@ -227,15 +232,9 @@ hipError_t by_epi(int epi, int id, const GemmArgs& g, hipStream_t s) {
     case EPI_PATCH: return by_id<BF, EPI_PATCH>(id, g, s);
     case EPI_SCORE: return by_id<BF, EPI_SCORE>(id, g, s);
     case EPI_FILTER: return by_id<BF, EPI_FILTER>(id, g, s);
-    case EPI_RANK:
-      if constexpr (!BF) return by_id<false, EPI_RANK>(id, g, s);
-      return hipErrorInvalidValue;
-    case EPI_LSE:
-      if constexpr (!BF) return by_id<false, EPI_LSE>(id, g, s);
-      return hipErrorInvalidValue;
-    case EPI_FILTER_MASK:
-      if constexpr (!BF) return by_id<false, EPI_FILTER_MASK>(id, g, s);
-      return hipErrorInvalidValue;
+    case EPI_RANK: return by_id_fp16<BF, EPI_RANK>(id, g, s);
+    case EPI_LSE: return by_id_fp16<BF, EPI_LSE>(id, g, s);
+    case EPI_FILTER_MASK: return by_id_fp16<BF, EPI_FILTER_MASK>(id, g, s);
     default: return hipErrorInvalidValue;
   }
 }

@@ -27,15 +27,19 @@ enum Epi {
                    // (column tile) * (wave columns of the config) + wave column < lse_slots(N): every
                    // slot a config uses is written once per live row, the others keep the caller's
                    // zeros. fp16, configs 1 and 8-11 only
-  EPI_FILTER_MASK = 8     // EPI_FILTER over the rows a bitset allows: column n is tested (and its cscale
-                          // loaded) only where bit n & 31 of mask[n >> 5] is set (bits at or past N
-                          // clear: mask_prepare). fp16, configs 1 and 8-11 only
+  EPI_FILTER_MASK = 8     // EPI_FILTER over the rows a bitset allows: column n is tested only where
+                          // bit n & 31 of mask[n >> 5] is set (bits at or past N clear:
+                          // mask_prepare). fp16, configs 1 and 8-11 only
 };
 // upper bound, over the configs EPI_LSE runs on, of the slab slots per row (wave column extents are
 // 64, 96 or 128 index rows)
 inline int64_t lse_slots(int64_t N) { return N / 64 + 4; }
 constexpr bool epi_stores16(int e) { return e == EPI_STORE || e == EPI_GELU; }
 constexpr bool epi_gelu(int e) { return e == EPI_GELU; }
+// the index passes' selecting epilogues: they compare each score with theta[m] and append / count / sum
+constexpr bool epi_selects(int e) {
+  return e == EPI_FILTER || e == EPI_FILTER_MASK || e == EPI_RANK || e == EPI_LSE;
+}
 
 struct GemmArgs {
   const u16* A; int64_t lda;
