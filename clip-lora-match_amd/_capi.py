@@ -112,6 +112,8 @@ def lib():
                                    c_void_p, c_int64, c_void_p]),
         "clm_topk_any": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int, c_int64, c_void_p,
                                  c_void_p, c_void_p]),
+        "clm_topk_distinct": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p,
+                                      c_void_p, c_void_p, c_void_p, c_void_p]),
         "clm_mask_rows": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_int64),
                                   c_void_p]),
         "clm_l2_normalize": (c_int, [c_int, c_void_p, c_int64, c_int, c_void_p]),
@@ -188,7 +190,7 @@ EXPORTED = (
     "clm_index_search_above", "clm_index_search_above_rows", "clm_index_search_above_read",
     "clm_index_search_masked",
     "clm_gemm_select", "clm_value_bounds",
-    "clm_topk_any", "clm_mask_rows",
+    "clm_topk_any", "clm_mask_rows", "clm_topk_distinct",
 )
 CLM_EPI_STORE, CLM_EPI_GELU, CLM_EPI_RESID, CLM_EPI_SCORE = 0, 1, 2, 4
 CLM_EPI_PATCH = 3   # clm_gemm_ex only

@@ -233,6 +233,24 @@ int clm_topk_merge(int hip_device, const float* scores, const int64_t* idx, int6
   return CLM_OK;
 }
 
+int clm_topk_distinct(int hip_device, const float* scores, const int64_t* idx, const int64_t* gid,
+                      const int64_t* offsets, int64_t ld, int64_t nq, int k, float* out_scores, int64_t* out_idx,
+                      int64_t* out_gid, int32_t* out_found, void* stream) {
+  if (nq < 0 || ld < 0 || k < 1 || k > 1024) return fail(CLM_E_ARG, "bad topk_distinct shape (nq, ld >= 0, 1 <= k <= 1024)");
+  if (nq == 0) return CLM_OK;
+  const bool reads = offsets || ld > 0;   // fixed-width lists of no entries read nothing
+  if (!out_scores || !out_idx || !out_gid || !out_found) return fail(CLM_E_ARG, "topk_distinct: a null output");
+  if (reads && (!scores || !idx || !gid)) return fail(CLM_E_ARG, "topk_distinct: a null list");
+  if (!is_device_ptr(out_scores) || !is_device_ptr(out_idx) || !is_device_ptr(out_gid) || !is_device_ptr(out_found) ||
+      (offsets && !is_device_ptr(offsets)) ||
+      (reads && (!is_device_ptr(scores) || !is_device_ptr(idx) || !is_device_ptr(gid))))
+    return fail(CLM_E_ARG, "topk_distinct: device pointers");
+  DeviceGuard g(hip_device);
+  KCHK(topk_distinct(scores, idx, gid, offsets, ld, nq, k, out_scores, out_idx, out_gid, out_found,
+                     (hipStream_t)stream));
+  return CLM_OK;
+}
+
 int clm_l2_normalize(int hip_device, float* rows, int64_t n, int dim, void* stream) {
   if (n < 0 || dim <= 0 || (n > 0 && !rows)) return fail(CLM_E_ARG, "bad argument");
   if (n == 0) return CLM_OK;

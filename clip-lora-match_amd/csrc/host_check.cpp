@@ -324,6 +324,19 @@ static void argument_checks() {
   }
   CHECK(clm_topk_merge(0, nullptr, nullptr, 1, 0, 1, 1, nullptr, nullptr, nullptr) != CLM_OK);
   CHECK(clm_l2_normalize(0, nullptr, 1, 0, nullptr) != CLM_OK);
+  // clm_topk_distinct: shape errors, null and host pointers are refused before anything runs
+  {
+    float hs[4] = {0.f, 0.f, 0.f, 0.f};
+    int64_t hi[4] = {0, 1, 2, 3}, ho[3] = {0, 2, 4};
+    int32_t hf[2] = {0, 0};
+    CHECK(clm_topk_distinct(0, nullptr, nullptr, nullptr, nullptr, 4, 0, 5, nullptr, nullptr, nullptr, nullptr, nullptr) == CLM_OK);
+    CHECK(clm_topk_distinct(0, nullptr, nullptr, nullptr, nullptr, 4, 1, 5, nullptr, nullptr, nullptr, nullptr, nullptr) == CLM_E_ARG);
+    CHECK(clm_topk_distinct(0, hs, hi, hi, nullptr, 4, 1, 0, hs, hi, hi, hf, nullptr) == CLM_E_ARG);
+    CHECK(clm_topk_distinct(0, hs, hi, hi, nullptr, 4, 1, 1025, hs, hi, hi, hf, nullptr) == CLM_E_ARG);
+    CHECK(clm_topk_distinct(0, hs, hi, hi, nullptr, 4, -1, 2, hs, hi, hi, hf, nullptr) == CLM_E_ARG);
+    CHECK(clm_topk_distinct(0, hs, hi, hi, nullptr, -4, 1, 2, hs, hi, hi, hf, nullptr) == CLM_E_ARG);
+    CHECK(clm_topk_distinct(0, hs, hi, hi, ho, 0, 2, 2, hs, hi, hi, hf, nullptr) == CLM_E_ARG);   // host memory
+  }
   CHECK(clm_scan16(0, nullptr, nullptr, -1, 64, nullptr, nullptr, 1, nullptr, 1, nullptr, nullptr, 0, nullptr) ==
         CLM_E_ARG);
   CHECK(clm_scan16(0, nullptr, nullptr, 256, 64, nullptr, nullptr, 1, nullptr, 1, nullptr, nullptr, 0, nullptr) ==

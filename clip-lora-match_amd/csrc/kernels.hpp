@@ -221,6 +221,14 @@ hipError_t kth_thresholds16(const u16* scores, int64_t lds, int64_t nq, int64_t 
 // asc); indices are any int64 >= 0 (< 0: an empty slot)
 hipError_t topk_merge(const float* in_s, const int64_t* in_i, int64_t nq, int parts, int k_in,
                       int k, float* out_s, int64_t* out_i, hipStream_t s);
+// the first k entries of each list that open a new group (k_group.hip): list q = entries [q * ld, q * ld +
+// ld) of in_s / in_i / in_g, or [offsets[q], offsets[q + 1]) with offsets; an entry with id < 0 (or gid <
+// 0) is skipped, an entry is kept iff no earlier position of its list has its gid. out_* [nq, k] = the
+// first k kept entries in list order, then (-inf, -1, -1); out_found [nq] = how many were written.
+// 1 <= k <= 1024; a pure function of the lists.
+hipError_t topk_distinct(const float* in_s, const int64_t* in_i, const int64_t* in_g, const int64_t* offsets,
+                         int64_t ld, int64_t nq, int k, float* out_s, int64_t* out_i, int64_t* out_g, int* out_found,
+                         hipStream_t s);
 // out[0] (device) = the largest index of idx[0, n), 0 if none is >= 0
 hipError_t max_index(const int64_t* idx, int64_t n, int64_t* out, hipStream_t s);
 hipError_t l2_normalize_rows(float* rows, int64_t n, int dim, hipStream_t s);

@@ -67,6 +67,18 @@ def gather_candidates(scores: torch.Tensor, idx: torch.Tensor, group=None) -> Tu
     return s_all, i_all
 
 
+def gather_lists(*lists: torch.Tensor, group=None) -> Tuple[torch.Tensor, ...]:
+    """gather_candidates for any number of [nq, k] tensors: each becomes [nq, world * k], rank-major"""
+    world = dist.get_world_size(group)
+    out = []
+    for t in lists:
+        nq, k = t.shape
+        buf = torch.empty((world * nq, k), dtype=t.dtype, device=t.device)
+        dist.all_gather_into_tensor(buf, t.contiguous(), group=group)
+        out.append(buf.view(world, nq, k).permute(1, 0, 2).reshape(nq, world * k))
+    return tuple(out)
+
+
 def merge_topk_gpu(scores: torch.Tensor, idx: torch.Tensor, parts: int, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
     """(score desc, index asc) merge of `parts` candidate lists per row on the GPU (clm_topk_merge)."""
     from . import _capi as C
@@ -79,6 +91,39 @@ def merge_topk_gpu(scores: torch.Tensor, idx: torch.Tensor, parts: int, k: int) 
     C.check(C.lib().clm_topk_merge(s.device.index, C.ptr(s), C.ptr(i), nq, parts, k_in, k, C.ptr(os_), C.ptr(oi),
                                    C.stream_of(s.device)), "clm_topk_merge")
     return os_, oi
+
+
+def merge_grouped_gpu(scores: torch.Tensor, idx: torch.Tensor, gids: torch.Tensor, parts: int,
+                      k: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Merge of the row shards' search_grouped lists on the GPU: scores / idx / gids [nq, parts * k_in]
+    -> (scores, idx, gids) [nq, k], the first k distinct groups of the concatenation in the search
+    order. clm_topk_merge orders all parts * k_in entries by (score desc, id asc); the gids follow
+    their ids (unique across shards, so a sort of the input ids finds each merged id's gid; an empty
+    slot keeps -1); clm_topk_distinct keeps each group's first entry. Exact: a group of the whole
+    index's answer is represented by its best row, that row's shard ranks the group among its own k
+    best groups (every group ahead of it there is ahead of it globally), and what other shards list
+    of the same group comes later in the order and is dropped. Past 8192 entries per query, or 1024
+    of them, clm_topk_merge takes ids below 2^32."""
+    from . import _capi as C
+    nq, n_in = scores.shape
+    if nq == 0 or n_in == 0:
+        dev = scores.device
+        return (torch.full((nq, k), float("-inf"), dtype=torch.float32, device=dev),
+                torch.full((nq, k), -1, dtype=torch.int64, device=dev),
+                torch.full((nq, k), -1, dtype=torch.int64, device=dev))
+    ms, mi = merge_topk_gpu(scores, idx, parts, n_in)
+    si, perm = idx.sort(dim=1)
+    pos = torch.searchsorted(si, mi.clamp(min=0)).clamp(max=n_in - 1)
+    mg = torch.where(mi >= 0, gids.gather(1, perm.gather(1, pos)), torch.full_like(mi, -1)).contiguous()
+    dev = ms.device
+    os_ = torch.empty((nq, k), dtype=torch.float32, device=dev)
+    oi = torch.empty((nq, k), dtype=torch.int64, device=dev)
+    og = torch.empty((nq, k), dtype=torch.int64, device=dev)
+    found = torch.empty((nq,), dtype=torch.int32, device=dev)
+    C.check(C.lib().clm_topk_distinct(dev.index, C.ptr(ms), C.ptr(mi), C.ptr(mg), None, n_in, nq, int(k),
+                                      C.ptr(os_), C.ptr(oi), C.ptr(og), C.ptr(found), C.stream_of(dev)),
+            "clm_topk_distinct")
+    return os_, oi, og
 
 
 def merge_lse(lses, errs=None) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -236,6 +281,37 @@ class ShardedIndex:
             return s, i
         s_all, i_all = gather_candidates(s, i, self.group)
         return merge(s_all, i_all, self.world, k)
+
+    def search_grouped(self, queries: torch.Tensor, k: int, groups, allow=None,
+                       merge: Callable = merge_grouped_gpu) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """CosineIndex.search_grouped over the whole sharded index (a collective call): (scores, idx,
+        gids) [nq, k], the k best distinct groups. groups: int64 [n_total] group ids of the WHOLE
+        index, the same on every rank (a group may span shards); allow: as in `search`. Each rank
+        searches its slice for its k best groups, one gather of the (score, id, gid) lists follows and
+        `merge` (merge_grouped_gpu) keeps the first k distinct groups of their union -- exact, see
+        there. A shard without rows or without an allowed row contributes (-inf, -1, -1) lists."""
+        g = torch.as_tensor(groups).reshape(-1)
+        if g.numel() != self.n_total:
+            raise ValueError(f"groups must hold one id per row of the whole index ({self.n_total}), got {g.numel()}")
+        mine = None
+        if allow is not None:
+            from .search import _allowed_rows
+            a = torch.as_tensor(allow)
+            keep = _allowed_rows(self.n_total, 0, keep=a) if a.dtype == torch.bool else \
+                _allowed_rows(self.n_total, 0, ids=a)
+            mine = keep[self.start: self.stop]
+        if len(self.local) == 0:   # an empty index refuses the call
+            nq = 1 if torch.as_tensor(queries).dim() == 1 else torch.as_tensor(queries).shape[0]
+            dev = getattr(self.local, "device", "cpu")
+            s = torch.full((nq, k), float("-inf"), dtype=torch.float32, device=dev)
+            i = torch.full((nq, k), -1, dtype=torch.int64, device=dev)
+            gi = torch.full((nq, k), -1, dtype=torch.int64, device=dev)
+        else:
+            s, i, gi = self.local.search_grouped(queries, k, g[self.start: self.stop], allow=mine)
+        if self.world == 1:
+            return s, i, gi
+        s_all, i_all, g_all = gather_lists(s, i, gi, group=self.group)
+        return merge(s_all, i_all, g_all, self.world, k)
 
     def search_above(self, queries: torch.Tensor, threshold):
         """CosineIndex.search_above over the whole sharded index (a collective call): each rank

@@ -200,9 +200,13 @@ class FinderIndex:
         self._unsaved = 0
         print(f"[FinderService] Index updated and saved to: {self.index_path}")
 
-    def search(self, query_emb: torch.Tensor, top_k: int = 5, where=None):
+    def search(self, query_emb: torch.Tensor, top_k: int = 5, where=None, group_by=None):
         """where: a row filter (TextSearchIndex.search_with_embedding's allow): a mask, item
-        positions, or a callable (i, image_path, text) -> bool -- only those items compete"""
+        positions, or a callable (i, image_path, text) -> bool -- only those items compete.
+        group_by: at most one result per group, its best row ("image_path", "text", a callable
+        (i, image_path, text) -> key, or group ids; TextSearchIndex.search_with_embedding's group_by)"""
+        if group_by is not None:
+            return self.index.search_with_embedding(query_emb, top_k=top_k, allow=where, group_by=group_by)
         if where is None:
             return self.index.search_with_embedding(query_emb, top_k=top_k)
         return self.index.search_with_embedding(query_emb, top_k=top_k, allow=where)

@@ -20,6 +20,10 @@ them in place (clm_index_remove / clm_index_update): an item handed back stops m
 corrected description changes its row, without the read-back / reset / re-append of the whole
 index; the result is bit for bit the index built from the final rows.
 
+.search_grouped (CosineIndex; group_by= on TextSearchIndex.search_*) answers "which k ITEMS match
+best" when an item owns several rows: the first k rows of the search order that open a new group
+(clm_topk_distinct), each group standing by its exact best row.
+
 Scores are the exact cosines of the stored fp32 rows (fp64 arithmetic, rounded
 once): the fp16 MFMA pass only bounds the candidates (clm_index_search). Top-k
 order is (score desc, index asc); CPU torch.topk leaves exact ties in arbitrary
@@ -82,6 +86,49 @@ def _allowed_rows(n: int, offset: int, keep=None, ids=None, exclude=None, device
         torch.ones((n,), dtype=torch.bool, device=device)
     out[loc] = ids is not None
     return out
+
+
+def unpack_mask(words: torch.Tensor, n: int) -> torch.Tensor:
+    """the inverse of pack_mask: mask words (int32 / uint32 storage) -> bool [n] on their device"""
+    w = torch.as_tensor(words).reshape(-1).to(torch.int64)
+    bits = (w[:, None] >> torch.arange(32, dtype=torch.int64, device=w.device)) & 1
+    return bits.reshape(-1)[:n].to(torch.bool)
+
+
+def group_row_bound(k: int, m: int) -> int:
+    """(k - 1) * m + 1: with at most m rows in a group, the first that many rows of any order hold k
+    distinct groups -- k - 1 groups fill at most (k - 1) * m of them (pigeonhole) -- or else every row"""
+    return (int(k) - 1) * int(m) + 1
+
+
+def group_ids_from_keys(keys) -> torch.Tensor:
+    """hashable keys [N] -> dense int64 group ids [N], numbered by first occurrence (CPU)"""
+    seen: dict = {}
+    return torch.tensor([seen.setdefault(key, len(seen)) for key in keys], dtype=torch.int64)
+
+
+GROUP_ROUTE_THRESHOLD = 1   # search_grouped(route=): every query by the threshold route
+GROUP_BLOCK_BUDGET = 1 << 25   # list entries one query block of the threshold route may hold
+
+
+@dataclass
+class GroupPlan:
+    """What search_grouped needs of a group assignment (CosineIndex.group_plan), reusable until the
+    index's rows change: gids [N] int64 on the device (local row order), the row filter as mask words
+    and as bool [N] (None: every row), n_allowed = the allowed rows, m = the most allowed rows any one
+    group holds, n_groups = the groups with an allowed row, reps = the mask words of one representative
+    per such group, its lowest allowed row. list_allow = the mask the list route searches under: the
+    filter, or -- without a filter, when the index holds rows that score NaN (a zero or non-finite norm)
+    -- all ones, because only the filtered search is bound to list NaN-scoring rows first; else None."""
+    gids: torch.Tensor
+    allow: Optional[torch.Tensor]
+    keep: Optional[torch.Tensor]
+    list_allow: Optional[torch.Tensor]
+    n: int
+    n_allowed: int
+    m: int
+    n_groups: int
+    reps: torch.Tensor
 
 
 class CosineIndex:
@@ -364,6 +411,171 @@ class CosineIndex:
                     torch.empty((0,), dtype=torch.float32, device=self.device))
         return torch.cat(pairs, 0), torch.cat(scores, 0)
 
+    # --------------------------------------------------------- grouped search --
+    def group_plan(self, groups, allow=None) -> GroupPlan:
+        """Validate a group assignment once for many searches. groups: int64-able integers [N] >= 0 in
+        local row order (row j of the index belongs to group groups[j]); allow: a row filter as `search`
+        takes it. ValueError for a wrong length, a negative id or a non-integer dtype. Torch ops, and
+        without a filter one single-query count_above pass that asks whether any row scores NaN
+        (GroupPlan.list_allow); valid until the index's rows change, like allow_mask()."""
+        n = len(self)
+        g = torch.as_tensor(groups)
+        if g.dtype in (torch.bool,) or g.is_floating_point() or g.is_complex():
+            raise ValueError(f"groups must hold integer group ids, got {g.dtype}")
+        g = g.reshape(-1)
+        if g.numel() != n:
+            raise ValueError(f"groups must hold one id per row ({n}), got {g.numel()}")
+        g = g.to(device=self.device, dtype=torch.int64).contiguous()
+        if n and int(g.min()) < 0:
+            raise ValueError("group ids must be >= 0")
+        words = keep = None
+        if allow is not None:
+            words = self._allow_words(allow)
+            if words.numel() != (n + 31) // 32:
+                raise ValueError(f"allow: a mask of {n} rows holds {(n + 31) // 32} words, got {words.numel()}")
+            keep = unpack_mask(words, n)
+        rows = torch.arange(n, device=self.device) if keep is None else torch.nonzero(keep).reshape(-1)
+        ga = g[rows]
+        m = n_groups = 0
+        rep = torch.zeros((n,), dtype=torch.bool, device=self.device)
+        if rows.numel():
+            order = torch.argsort(ga, stable=True)   # rows ascending inside a group
+            gs = ga[order]
+            first = torch.ones_like(gs, dtype=torch.bool)
+            first[1:] = gs[1:] != gs[:-1]
+            starts = torch.nonzero(first).reshape(-1)
+            counts = torch.diff(starts, append=torch.tensor([gs.numel()], device=self.device))
+            m, n_groups = int(counts.max()), int(starts.numel())
+            rep[rows[order[starts]]] = True
+        list_allow = words
+        if words is None and n:
+            # a row of zero or non-finite norm scores NaN against any query, and leads the order; the
+            # unfiltered search's MFMA routes cannot list such rows, the filtered search always does
+            probe = torch.ones((1, self.dim), dtype=torch.float32, device=self.device)
+            if int(self.count_above(probe, torch.tensor([float("nan")]), torch.tensor([2 ** 63 - 1]))[0]) > 0:
+                list_allow = pack_mask(torch.ones((n,), dtype=torch.bool, device=self.device))
+        return GroupPlan(gids=g, allow=words, keep=keep, list_allow=list_allow, n=n, n_allowed=int(rows.numel()),
+                         m=m, n_groups=n_groups, reps=pack_mask(rep))
+
+    def _topk_distinct(self, s, i, g, k: int, offsets=None):
+        """clm_topk_distinct over fixed-width [nq, ld] lists, or ragged ones through offsets [nq + 1]"""
+        s, i, g = s.contiguous(), i.contiguous(), g.contiguous()
+        if offsets is None:
+            nq, ld = s.shape
+        else:
+            offsets = offsets.to(device=self.device, dtype=torch.int64).contiguous()
+            nq, ld = offsets.numel() - 1, 0
+        os_ = torch.empty((nq, k), dtype=torch.float32, device=self.device)
+        oi = torch.empty((nq, k), dtype=torch.int64, device=self.device)
+        og = torch.empty((nq, k), dtype=torch.int64, device=self.device)
+        found = torch.empty((nq,), dtype=torch.int32, device=self.device)
+        if nq == 0 or s.numel() == 0:   # no entry anywhere (an empty tensor has no pointer to pass)
+            return os_.fill_(float("-inf")), oi.fill_(-1), og.fill_(-1), found.zero_()
+        C.check(C.lib().clm_topk_distinct(self.device.index, C.ptr(s), C.ptr(i), C.ptr(g),
+                                          C.ptr(offsets) if offsets is not None else None, ld, nq, int(k),
+                                          C.ptr(os_), C.ptr(oi), C.ptr(og), C.ptr(found), C.stream_of(self.device)),
+                "clm_topk_distinct")
+        return os_, oi, og, found
+
+    def search_grouped(self, queries, k: int, groups, allow=None, route: int = 0,
+                       block_budget: int = GROUP_BLOCK_BUDGET) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """The k best DISTINCT groups: (scores [nq, k] f32, idx [nq, k] i64, gids [nq, k] i64) on the GPU.
+        Walk the rows in the order of `search` (NaN first, exact score desc, global id asc; with allow=
+        only the allowed rows) and keep a row iff no earlier row belongs to its group: the result is the
+        first k kept rows -- each group stands by its exact best row, ties by id --, scores bit for bit
+        those of `search`, (-inf, -1, -1) past the number of distinct allowed groups. groups: int64 [N]
+        ids >= 0 in local row order, or a group_plan() (which then holds the filter: allow must be None).
+        k in [1, 1024].
+        List route: with at most m allowed rows per group the first (k - 1) m + 1 rows of the order hold
+        k groups or every row (group_row_bound), so search(q, L), L = min(that bound, 1024, allowed
+        rows), and clm_topk_distinct over the list answer every query that found k groups -- and all of
+        them when L is the bound or every allowed row. (An index that holds NaN-scoring rows is searched
+        under an all-ones filter, GroupPlan.list_allow: those rows lead the order.)
+        Threshold route, for the rest: theta = the k-th best score among one representative row per
+        group (search(q, k, allow=plan.reps); -inf with fewer than k groups) is <= the k-th best group's
+        score, so search_above(q, theta) lists every
+        answer row in order; rows outside the filter are struck out and clm_topk_distinct runs over the
+        ragged lists, in query blocks of at most block_budget list entries (count_above gives the
+        lengths; a single query may exceed it alone). route: 0, or GROUP_ROUTE_THRESHOLD to send every
+        query by the threshold route; the results do not depend on it (group_stats says who served).
+        The threshold route runs search_above, so it REPLACES the index's held threshold-search result
+        (clm_index_search_above_read); results search_above() already returned are copies and stay.
+        ValueError for an empty index, k outside [1, 1024], or groups that group_plan refuses."""
+        k = int(k)
+        if not 1 <= k <= 1024:
+            raise ValueError(f"search_grouped: k must be in [1, 1024], got {k}")
+        n = len(self)
+        if n == 0:
+            raise ValueError("search_grouped: the index is empty")
+        if isinstance(groups, GroupPlan):
+            if allow is not None:
+                raise ValueError("search_grouped: a group_plan() holds its own filter; pass allow to group_plan")
+            plan = groups
+        else:
+            plan = self.group_plan(groups, allow)
+        if plan.n != n:
+            raise ValueError(f"search_grouped: the plan was made for {plan.n} rows, the index holds {n}")
+        q = torch.as_tensor(queries)
+        if q.dim() == 1:
+            q = q.unsqueeze(0)
+        if q.dim() != 2 or q.shape[1] != self.dim:
+            raise ValueError(f"queries must be [nq, {self.dim}], got {tuple(q.shape)}")
+        q = q.to(self.device)   # unpadded: search / search_above / count_above take it as the caller's
+        nq, offset = q.shape[0], int(getattr(self, "_offset", 0))
+        stats = self._group_counters()
+        out_s = torch.full((nq, k), float("-inf"), dtype=torch.float32, device=self.device)
+        out_i = torch.full((nq, k), -1, dtype=torch.int64, device=self.device)
+        out_g = torch.full((nq, k), -1, dtype=torch.int64, device=self.device)
+        if nq == 0:
+            return out_s, out_i, out_g
+        if plan.n_allowed == 0:   # nothing competes: every slot is a pad
+            stats["threshold" if int(route) == GROUP_ROUTE_THRESHOLD else "list"] += nq
+            return out_s, out_i, out_g
+        todo = torch.arange(nq, device=self.device)
+        if int(route) != GROUP_ROUTE_THRESHOLD:
+            bound = group_row_bound(k, plan.m)
+            L = min(bound, 1024, plan.n_allowed)
+            ls, li = self.search(q, L, allow=plan.list_allow) if plan.list_allow is not None else self.search(q, L)
+            lg = torch.where(li >= 0, plan.gids[(li - offset).clamp(min=0)], torch.full_like(li, -1))
+            out_s, out_i, out_g, found = self._topk_distinct(ls, li, lg, k)
+            if L == bound or L == plan.n_allowed:
+                todo = todo[:0]
+            else:
+                todo = torch.nonzero(found < k).reshape(-1)
+            stats["list"] += nq - int(todo.numel())
+        if todo.numel() == 0:
+            return out_s, out_i, out_g
+        stats["threshold"] += int(todo.numel())
+        qs = q[todo]
+        theta = self.search(qs, k, allow=plan.reps)[0][:, k - 1].contiguous()
+        lens = self.count_above(qs, theta, torch.full((qs.shape[0],), 2 ** 63 - 1, dtype=torch.int64)).tolist()
+        b0 = 0
+        while b0 < len(lens):
+            b1, total = b0 + 1, lens[b0]
+            while b1 < len(lens) and total + lens[b1] <= int(block_budget):
+                total += lens[b1]
+                b1 += 1
+            off, ts, ti = self.search_above(qs[b0:b1], theta[b0:b1])
+            loc = ti - offset
+            tg = plan.gids[loc]
+            if plan.keep is not None:
+                ti = torch.where(plan.keep[loc], ti, torch.full_like(ti, -1))
+            bs, bi, bg, _ = self._topk_distinct(ts, ti, tg, k, offsets=off)
+            rows = todo[b0:b1]
+            out_s[rows], out_i[rows], out_g[rows] = bs, bi, bg
+            b0 = b1
+        return out_s, out_i, out_g
+
+    def group_stats(self) -> dict:
+        """search_grouped queries answered by the list route (`list`) and by the threshold route
+        (`threshold`), counted in Python since the index was made"""
+        return dict(self._group_counters())
+
+    def _group_counters(self) -> dict:
+        if not hasattr(self, "_group_stats"):
+            self._group_stats = {"list": 0, "threshold": 0}
+        return self._group_stats
+
     # ------------------------------------------------------------ log-sum-exp --
     def logsumexp(self, queries, scale: float, head: int = 64, band_cap: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
         """(lse [nq] f64, err [nq] f32) on the GPU: lse = log sum_j exp(scale * score_j) over every row
@@ -639,23 +851,48 @@ class TextSearchIndex:
             return torch.tensor(keep, dtype=torch.bool)
         return allow
 
-    def search_batch(self, queries, top_k: int = 5, allow=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    def group_ids(self, group_by) -> torch.Tensor:
+        """int64 group ids [num_items] (CPU) from a group_by= argument: "image_path" or "text" -- rows
+        with equal metadata form a group, a row without that entry is a group of its own --, a callable
+        (i, image_path, text) -> hashable key, or an int sequence / tensor [num_items] taken as the
+        ids themselves. Keys map to dense ids by first occurrence (group_ids_from_keys)."""
+        n = self.num_items
+        if isinstance(group_by, str):
+            if group_by not in ("image_path", "text"):
+                raise ValueError(f'group_by must be "image_path", "text", a callable or group ids, got {group_by!r}')
+            meta = self.image_paths if group_by == "image_path" else self.texts
+            return group_ids_from_keys([("key", meta[i]) if i < len(meta) else ("row", i) for i in range(n)])
+        if callable(group_by):
+            return group_ids_from_keys([group_by(i, self.image_paths[i] if i < len(self.image_paths) else "",
+                                                 self.texts[i] if i < len(self.texts) else "") for i in range(n)])
+        return torch.as_tensor(group_by)   # CosineIndex.group_plan validates length, dtype and sign
+
+    def search_batch(self, queries, top_k: int = 5, allow=None, group_by=None):
         """[nq, d] queries -> (scores [nq, k], indices [nq, k]) on the GPU, k = min(top_k, num_items).
-        allow: only these rows compete (see _allow); slots past their number hold (-inf, -1)."""
+        allow: only these rows compete (see _allow); slots past their number hold (-inf, -1).
+        group_by (see group_ids; or a CosineIndex.group_plan(), which holds its own filter): at most one
+        row per group, its best -- (scores, indices, group ids), (-inf, -1, -1) past the number of
+        distinct allowed groups (CosineIndex.search_grouped; top_k <= 1024)."""
         k = min(int(top_k), self.num_items)
         if k < 0:
             raise RuntimeError("selected index k out of range")
         if k == 0:
             q = torch.as_tensor(queries)
             nq = 1 if q.dim() == 1 else q.shape[0]
-            return torch.empty((nq, 0)), torch.empty((nq, 0), dtype=torch.int64)
+            empty = (torch.empty((nq, 0)), torch.empty((nq, 0), dtype=torch.int64))
+            return empty if group_by is None else empty + (torch.empty((nq, 0), dtype=torch.int64),)
+        if group_by is not None:
+            groups = group_by if isinstance(group_by, GroupPlan) else self.group_ids(group_by)
+            return self._gpu.search_grouped(queries, k, groups, allow=None if allow is None else self._allow(allow))
         if allow is not None:
             return self._gpu.search(queries, k, allow=self._allow(allow))
         return self._gpu.search(queries, k)
 
-    def search_with_embedding(self, query_emb: torch.Tensor, top_k: int = 5, allow=None) -> List[SearchResult]:
+    def search_with_embedding(self, query_emb: torch.Tensor, top_k: int = 5, allow=None,
+                              group_by=None) -> List[SearchResult]:
         """query_emb: shape (d,) atau (1, d). allow: a row filter (search_batch); fewer than top_k
-        results when fewer rows are allowed."""
+        results when fewer rows are allowed. group_by (search_batch): at most one SearchResult per
+        group, the group's best row; fewer than top_k when fewer groups compete."""
         query_emb = torch.as_tensor(query_emb)
         if query_emb.ndim == 1:
             query_emb = query_emb.unsqueeze(0)
@@ -663,13 +900,15 @@ class TextSearchIndex:
             raise ValueError(f"query_emb must be shape (d,) or (1, d), got {tuple(query_emb.shape)}")
         if query_emb.shape[-1] != self.dim:
             raise ValueError(f"query_emb dim {query_emb.shape[-1]} != index dim {self.dim}")
-        if allow is None:   # today's call, untouched
+        if group_by is not None:
+            scores, indices, _ = self.search_batch(query_emb, top_k, allow=allow, group_by=group_by)
+        elif allow is None:   # today's call, untouched
             scores, indices = self.search_batch(query_emb, top_k)
         else:
             scores, indices = self.search_batch(query_emb, top_k, allow=allow)
         results: List[SearchResult] = []
         for idx, score in zip(indices[0].tolist(), scores[0].tolist()):
-            if allow is not None and idx < 0:   # the pad of a short filtered list
+            if (allow is not None or group_by is not None) and idx < 0:   # the pad of a short list
                 continue
             # an index outside [0, len) has no metadata: the (-inf, -1) pad of a short result must
             # not read the last item's through Python's negative indexing
@@ -678,14 +917,21 @@ class TextSearchIndex:
             results.append(SearchResult(index=idx, score=float(score), image_path=img, text=txt))
         return results
 
-    def search_by_text(self, query, model, processor, device, top_k: int = 5, allow=None) -> List[SearchResult]:
+    def search_by_text(self, query, model, processor, device, top_k: int = 5, allow=None,
+                       group_by=None) -> List[SearchResult]:
         from .clip_model import encode_text
-        return self.search_with_embedding(encode_text(query, model, processor, device), top_k=top_k, allow=allow)
+        emb = encode_text(query, model, processor, device)
+        if group_by is None:
+            return self.search_with_embedding(emb, top_k=top_k, allow=allow)
+        return self.search_with_embedding(emb, top_k=top_k, allow=allow, group_by=group_by)
 
-    def search_by_image(self, image_path, model, processor, device, top_k: int = 5, allow=None) -> List[SearchResult]:
+    def search_by_image(self, image_path, model, processor, device, top_k: int = 5, allow=None,
+                        group_by=None) -> List[SearchResult]:
         from .clip_model import encode_image
-        return self.search_with_embedding(encode_image(image_path, model, processor, device), top_k=top_k,
-                                          allow=allow)
+        emb = encode_image(image_path, model, processor, device)
+        if group_by is None:
+            return self.search_with_embedding(emb, top_k=top_k, allow=allow)
+        return self.search_with_embedding(emb, top_k=top_k, allow=allow, group_by=group_by)
 
     def search_above_with_embedding(self, query_emb: torch.Tensor, threshold: float) -> List[SearchResult]:
         """Every item whose cosine with the query is >= threshold (CosineIndex.search_above), best

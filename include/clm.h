@@ -35,6 +35,10 @@
  *   clm_cosine_scores          cosine_similarity similarity.py:10-33
  *   clm_topk_merge             (new) merge of per-shard top-k lists for the
  *                              8-GPU sharded search
+ *   clm_topk_distinct          (new) the first k entries of an ordered list that open a new group:
+ *                              "the k best ITEMS" where an item owns several rows (the finder
+ *                              stores a photo and a description per item; a CSV index lists one
+ *                              image_path under several captions)
  *   clm_l2_normalize           v / ||v||_2 (clip_model.py:116,148; search.py:68,93)
  *   clm_index_remove/_update   (new) the second half of the lost-and-found lifecycle: an item handed
  *                              back stops matching, a corrected description replaces its row --
@@ -502,6 +506,27 @@ int clm_topk_any(int hip_device, const float* scores, int64_t lds, const int64_t
  * CLM_E_ARG, nothing written: N < 1 or > 2^32 - 1, a pointer that is not device memory. */
 int clm_mask_rows(int hip_device, const uint32_t* allow, int64_t N, uint32_t* words, uint32_t* bcnt, int64_t* boff,
                   uint32_t* list, int64_t* P_out, void* stream);
+/* clm_topk_distinct: the first k entries of a list that open a new group -- the selection step of the
+ * grouped (collapse) search, CosineIndex.search_grouped and distributed.merge_grouped_gpu. Device pointers.
+ * Query q owns a list of entries (scores f32, idx i64, gid i64), already in the search order: entries
+ * [q * ld, (q + 1) * ld) of the three arrays (offsets == NULL: fixed width), or [offsets[q], offsets[q + 1])
+ * with offsets [nq + 1] i64 (the shape clm_index_search_above returns). An entry with idx < 0 (a pad, or a
+ * row the caller struck out) is skipped wherever it stands, as is one with gid < 0. An entry is KEPT iff no
+ * earlier position of its list carries its gid. out_scores / out_idx / out_gid [nq, k] = the first k kept
+ * entries in list order -- each with its score, idx and gid bit for bit as given --, then (-inf, -1, -1);
+ * out_found [nq] i32 = the number of kept entries written (<= k).
+ * gid is any int64 >= 0: the set of gids seen is a hash table in LDS keyed by the whole value, so values
+ * that share a slot are still told apart. The result is a pure function of the lists: where several
+ * positions carry a gid the lowest one wins (an integer minimum, not arrival order), and the output slots
+ * are prefix sums in list order; two calls return the same bits. One workgroup per list walks it in chunks
+ * of 1024 entries and stops at k kept; a list has any length (64-bit offsets). The call does not drain the
+ * stream.
+ * CLM_E_ARG, nothing written: k outside [1, 1024], nq < 0, ld < 0, and with nq > 0 a null output, a null
+ * list array (unless offsets == NULL and ld == 0), or a pointer that is not device memory. nq == 0 is
+ * CLM_OK. The extents are the caller's to provide: offsets must be non-decreasing and inside the arrays. */
+int clm_topk_distinct(int hip_device, const float* scores, const int64_t* idx, const int64_t* gid,
+                      const int64_t* offsets, int64_t ld, int64_t nq, int k, float* out_scores, int64_t* out_idx,
+                      int64_t* out_gid, int32_t* out_found, void* stream);
 /* attention over qkv [B*T, 3*H*64] (q pre-scaled by 64^-1/2), out [B*T, ldo] (device
  * pointers); causal: 0 / non-0 switch (the text tower's mask). */
 int clm_attention(int hip_device, int dtype, int causal, const void* qkv, void* out, int64_t ldo,
