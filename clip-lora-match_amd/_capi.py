@@ -88,6 +88,8 @@ def lib():
         "clm_index_search": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p]),
         "clm_index_search_masked": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p, c_int, c_void_p, c_void_p,
                                             c_void_p]),
+        "clm_index_search_keyed": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_void_p,
+                                           c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
         "clm_index_count_above": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_int,
                                           c_void_p]),
         "clm_index_rank": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
@@ -136,6 +138,9 @@ def lib():
                                     c_void_p, c_void_p, c_void_p, c_int64, c_float, c_void_p, c_void_p, c_void_p,
                                     c_int, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_void_p, c_int,
                                     c_void_p]),
+        "clm_gemm_select_keyed": (c_int, [c_int, c_int, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int,
+                                          c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int,
+                                          c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
         "clm_value_bounds": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_void_p]),
         "clm_debug_set": (None, [c_int]),
         "clm_attention": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p]),
@@ -191,10 +196,12 @@ EXPORTED = (
     "clm_index_search_masked",
     "clm_gemm_select", "clm_value_bounds",
     "clm_topk_any", "clm_mask_rows", "clm_topk_distinct",
+    "clm_index_search_keyed", "clm_gemm_select_keyed",
 )
 CLM_EPI_STORE, CLM_EPI_GELU, CLM_EPI_RESID, CLM_EPI_SCORE = 0, 1, 2, 4
 CLM_EPI_PATCH = 3   # clm_gemm_ex only
 CLM_EPI_FILTER, CLM_EPI_RANK, CLM_EPI_LSE, CLM_EPI_FILTER_MASK = 5, 6, 7, 8   # clm_gemm_select only
+CLM_EPI_FILTER_KEYS = 9   # clm_gemm_select_keyed only
 CLM_PROF_GEMM, CLM_PROF_ATTN, CLM_PROF_LN, CLM_PROF_OTHER = 0, 1, 2, 3
 
 

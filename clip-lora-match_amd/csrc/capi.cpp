@@ -875,14 +875,14 @@ int clm_gemm_scores16(int hip_device, int config, const void* A, int64_t lda, co
 
 // test hook: the index passes' selecting epilogues alone (EPI_FILTER / EPI_RANK / EPI_LSE /
 // EPI_FILTER_MASK, gemm_common.hpp), with every GemmArgs field the search sets for them. Nothing is
-// zeroed here: cnt, above and the slab are the caller's, as in the search.
-int clm_gemm_select(int hip_device, int epilogue, int config, const void* A, int64_t lda, const void* W, int64_t ldw,
-                    int M, int N, int K, const float* rscale, const float* cscale, const float* theta,
-                    int64_t theta_ld, float margin, int* cnt, float* cand_s, int64_t* cand_i, int cap, int64_t base,
-                    const uint32_t* cbound, uint32_t* above, float* lse_part, int64_t lse_ld, float lse_c,
-                    const uint32_t* mask, int m_fastest, void* stream) {
-  if (!epi_selects(epilogue))
-    return fail(CLM_E_ARG, "gemm_select: epilogue must be FILTER, RANK, LSE or FILTER_MASK");
+// zeroed here: cnt, above and the slab are the caller's, as in the search. (clm_gemm_select_keyed
+// below: EPI_FILTER_KEYS, whose keys and ranges clm_gemm_select's signature has no room for.)
+static int gemm_select_run(int hip_device, int epilogue, int config, const void* A, int64_t lda, const void* W,
+                           int64_t ldw, int M, int N, int K, const float* rscale, const float* cscale,
+                           const float* theta, int64_t theta_ld, float margin, int* cnt, float* cand_s,
+                           int64_t* cand_i, int cap, int64_t base, const uint32_t* cbound, uint32_t* above,
+                           float* lse_part, int64_t lse_ld, float lse_c, const uint32_t* mask, const int32_t* keys,
+                           const int32_t* klo, const int32_t* khi, int m_fastest, void* stream) {
   if (config >= gemm_num_configs()) return fail(CLM_E_ARG, "bad config");
   if (M < 0 || N < 0 || K <= 0 || K % 64 || lda % 8 || ldw % 8 || lda < K || ldw < K)
     return fail(CLM_E_ARG, "bad shape (K % 64 == 0; lda, ldw multiples of 8 and >= K)");
@@ -890,22 +890,47 @@ int clm_gemm_select(int hip_device, int epilogue, int config, const void* A, int
   if (epilogue == EPI_LSE && lse_ld < lse_slots(N)) return fail(CLM_E_ARG, "gemm_select: lse_ld < N / 64 + 4");
   if (M == 0 || N == 0) return CLM_OK;
   if (!A || !W || !cscale || !theta || !cnt || !cand_i) return fail(CLM_E_ARG, "gemm_select: null pointer");
-  if ((epilogue == EPI_FILTER || epilogue == EPI_FILTER_MASK) && !cand_s)
-    return fail(CLM_E_ARG, "gemm_select: FILTER / FILTER_MASK write cand_s");
+  if ((epilogue == EPI_FILTER || epilogue == EPI_FILTER_MASK || epilogue == EPI_FILTER_KEYS) && !cand_s)
+    return fail(CLM_E_ARG, "gemm_select: FILTER / FILTER_MASK / FILTER_KEYS write cand_s");
   if (epilogue == EPI_RANK && !above) return fail(CLM_E_ARG, "gemm_select: RANK counts into above");
   if (epilogue == EPI_LSE && !lse_part) return fail(CLM_E_ARG, "gemm_select: LSE writes lse_part");
   if (epilogue == EPI_FILTER_MASK && !mask) return fail(CLM_E_ARG, "gemm_select: FILTER_MASK reads mask");
+  if (epilogue == EPI_FILTER_KEYS && (!keys || !klo || !khi || ((uintptr_t)keys & 15)))
+    return fail(CLM_E_ARG, "gemm_select: FILTER_KEYS reads keys (16-byte aligned), klo and khi");
   DeviceGuard g(hip_device);
   GemmArgs a{};
   a.A = (const u16*)A; a.lda = lda; a.W = (const u16*)W; a.ldw = ldw; a.M = M; a.N = N; a.K = K;
   a.rscale = rscale; a.cscale = cscale; a.theta = theta; a.theta_ld = theta_ld; a.rank_margin = margin;
   a.cnt = cnt; a.cand_s = cand_s; a.cand_i = cand_i; a.cap = cap; a.base = base; a.cbound = cbound;
   a.above = above; a.lse_part = lse_part; a.lse_ld = lse_ld; a.lse_c = lse_c; a.mask = mask;
+  a.keys = keys; a.klo = klo; a.khi = khi;
   a.m_fastest = m_fastest ? 1 : 0;
   a.debug = g_gemm_debug;
   hipError_t e = gemm_cfg(false, epilogue, config, a, (hipStream_t)stream);
   if (e != hipSuccess) return fail(CLM_E_HIP, std::string("gemm: ") + hipGetErrorString(e));
   return CLM_OK;
+}
+
+int clm_gemm_select(int hip_device, int epilogue, int config, const void* A, int64_t lda, const void* W, int64_t ldw,
+                    int M, int N, int K, const float* rscale, const float* cscale, const float* theta,
+                    int64_t theta_ld, float margin, int* cnt, float* cand_s, int64_t* cand_i, int cap, int64_t base,
+                    const uint32_t* cbound, uint32_t* above, float* lse_part, int64_t lse_ld, float lse_c,
+                    const uint32_t* mask, int m_fastest, void* stream) {
+  if (!epi_selects(epilogue) || epilogue == EPI_FILTER_KEYS)
+    return fail(CLM_E_ARG, "gemm_select: epilogue must be FILTER, RANK, LSE or FILTER_MASK");
+  return gemm_select_run(hip_device, epilogue, config, A, lda, W, ldw, M, N, K, rscale, cscale, theta, theta_ld, margin,
+                         cnt, cand_s, cand_i, cap, base, cbound, above, lse_part, lse_ld, lse_c, mask, nullptr,
+                         nullptr, nullptr, m_fastest, stream);
+}
+
+int clm_gemm_select_keyed(int hip_device, int config, const void* A, int64_t lda, const void* W, int64_t ldw, int M,
+                          int N, int K, const float* rscale, const float* cscale, const float* theta,
+                          int64_t theta_ld, int* cnt, float* cand_s, int64_t* cand_i, int cap, int64_t base,
+                          const uint32_t* cbound, const int32_t* keys, const int32_t* klo, const int32_t* khi,
+                          int m_fastest, void* stream) {
+  return gemm_select_run(hip_device, EPI_FILTER_KEYS, config, A, lda, W, ldw, M, N, K, rscale, cscale, theta, theta_ld,
+                         0.f, cnt, cand_s, cand_i, cap, base, cbound, nullptr, nullptr, 0, 0.f, nullptr, keys, klo, khi,
+                         m_fastest, stream);
 }
 
 // test hook: the order keys of min / max cscale (value_bounds, k_search.hip), the cbound of the index passes

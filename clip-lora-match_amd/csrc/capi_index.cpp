@@ -402,12 +402,13 @@ int clm_index_stats(const clm_index* x, int64_t* filtered, int64_t* exact, int64
 
 int clm_index_stats2(const clm_index* x, int64_t* out, int n) {
   if (!x || !out || n < 0) return fail(CLM_E_ARG, "bad argument");
-  const int64_t v[20] = {x->search_stats[0], x->search_stats[3], x->search_stats[1], x->search_stats[2],
+  const int64_t v[22] = {x->search_stats[0], x->search_stats[3], x->search_stats[1], x->search_stats[2],
                          x->search_stats[4], x->search_stats[5], x->search_stats[6], x->search_stats[7],
                          x->search_stats[8], x->search_stats[9], x->search_stats[10], x->search_stats[11],
                          x->search_stats[12], x->search_stats[13], x->search_stats[14], x->search_stats[15],
-                         x->search_stats[16], x->search_stats[17], x->search_stats[18], x->search_stats[19]};
-  for (int i = 0; i < n && i < 20; ++i) out[i] = v[i];
+                         x->search_stats[16], x->search_stats[17], x->search_stats[18], x->search_stats[19],
+                         x->search_stats[20], x->search_stats[21]};
+  for (int i = 0; i < n && i < 22; ++i) out[i] = v[i];
   return CLM_OK;
 }
 

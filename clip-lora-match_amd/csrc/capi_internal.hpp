@@ -110,7 +110,9 @@ struct clm_index {
   // those whose candidate list overflowed its capacity
   // [17] / [18] / [19]: masked-search queries served by the pass route / the gather route / the exact
   // route (a pass-route query redone exactly counts in [19])
-  int64_t search_stats[20] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  // [20] / [21]: keyed-search queries served by the pass route / the exact route (a redone query counts
+  // in [21])
+  int64_t search_stats[22] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   // The held result of the last threshold search (clm_index_search_above / _rows): res_n entries
   // (exact score, global id) in CSR order, read by clm_index_search_above_read until the next
   // threshold search, reset, mutation or destroy (res_valid). rg_comp / rg_comp2: the composites it

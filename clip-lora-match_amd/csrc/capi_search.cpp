@@ -178,11 +178,16 @@ constexpr int CAND_CAP = 2048;
 
 // Chunked scan: score chunks [nqb, ch] -- fp16 MFMA (EPI_SCORE GEMM) or exact fp64 cosines
 // (exact_scores) -- radix top-k per chunk row, merge of the chunk lists. Any k <= 1024, any N.
-// allow (exact scan only): the prepared words of a filtered search -- every window's disallowed
-// entries become -inf before its top-k (mask_fill), so they sort behind every allowed row
+// allow (exact scan only): the filter of a filtered search -- its prepared words -- or of a keyed one
+// -- the keys [N] and the ranges of these nq queries. Every window's disallowed entries become -inf
+// before its top-k (mask_fill / key_fill), so they sort behind every allowed row
+struct ScanFilter {
+  const uint32_t* words = nullptr;
+  const int32_t *keys = nullptr, *lo = nullptr, *hi = nullptr;
+};
 static int search_scan(clm_index* x, bool exact, const u16* q16, const float* qinv, const float* q32,
                        const double* qn, int64_t nq, int k, float* osc, int64_t* oix, hipStream_t st,
-                       const uint32_t* allow = nullptr) {
+                       const ScanFilter& allow = ScanFilter{}) {
   const int dim = (int)x->dim;
   const int64_t N = x->n;
   const size_t budget = (size_t)512 << 20;
@@ -216,7 +221,8 @@ static int search_scan(clm_index* x, bool exact, const u16* q16, const float* qi
       if (exact) {
         const ExactRows er = exact_rows(x, r0);
         KCHK(exact_scores(q32 + q0 * dim, qn + q0, nb, er.p, er.f16, rn, dim, sc, ch, st));
-        if (allow) KCHK(mask_fill(sc, ch, nb, rn, r0, allow, st));
+        if (allow.words) KCHK(mask_fill(sc, ch, nb, rn, r0, allow.words, st));
+        if (allow.keys) KCHK(key_fill(sc, ch, nb, rn, r0, allow.keys, allow.lo + q0, allow.hi + q0, st));
       } else {
         GemmArgs ga{};
         ga.A = q16 + q0 * dim; ga.lda = dim; ga.W = x->rows + r0 * dim; ga.ldw = dim;
@@ -803,7 +809,7 @@ constexpr double MASK_GATHER_SMALL = (double)(1 << 20);
 
 static int masked_exact(clm_index* x, const QueryStage& qs, int64_t nq, int k, const uint32_t* words, float* osc,
                         int64_t* oix, hipStream_t st) {
-  int r = search_scan(x, true, nullptr, nullptr, qs.q32, qs.qn, nq, k, osc, oix, st, words);
+  int r = search_scan(x, true, nullptr, nullptr, qs.q32, qs.qn, nq, k, osc, oix, st, ScanFilter{words});
   if (r) return r;
   KCHK(map_ids(osc, oix, nq * k, nullptr, 0, st));
   return CLM_OK;
@@ -815,7 +821,8 @@ static int masked_redo(clm_index* x, const QueryStage& qs, int k, const uint32_t
   return redo_subset(x, redo, {{qs.q32, x->dim * 4}, {qs.qn, 8}}, {{osc, (int64_t)k * 4}, {oix, (int64_t)k * 8}},
                      "masked redo", st, [&](void* const* in, void* const* out) -> int {
                        int r = search_scan(x, true, nullptr, nullptr, (const float*)in[0], (const double*)in[1],
-                                           (int64_t)redo.size(), k, (float*)out[0], (int64_t*)out[1], st, words);
+                                           (int64_t)redo.size(), k, (float*)out[0], (int64_t*)out[1], st,
+                                           ScanFilter{words});
                        if (r) return r;
                        KCHK(map_ids((const float*)out[0], (int64_t*)out[1], (int64_t)redo.size() * k, nullptr, 0, st));
                        return CLM_OK;
@@ -1051,6 +1058,177 @@ int clm_mask_rows(int hip_device, const uint32_t* allow, int64_t N, uint32_t* wo
     HIPCHK(hipStreamSynchronize(st));
   }
   if (P_out) *P_out = P;
+  return CLM_OK;
+}
+
+// ---- keyed search (clm_index_search_keyed) --------------------------------------------------
+// One int32 key per index row (the caller's, per call) and one inclusive key range per query: row j
+// is open to query i iff lo[i] <= keys[j] <= hi[i]. Row i of the result is row 0 of the masked
+// search of query i alone under the mask of its open rows. Two routes:
+//  A exact:  search_scan(exact) with every window's closed entries set to -inf (key_fill);
+//  C pass:   theta[i] from a strided sample of the index whose closed entries are struck out per
+//            query (key_fill on the sample's score matrix): the k-th best of sample rows that are in
+//            the index and open to the query is never above the k-th best of all its open rows, and a
+//            query with fewer than k open sample rows gets -inf and lists every open row. Then one
+//            EPI_FILTER_KEYS pass and rescore_select; a query whose list overflowed CAND_CAP or ended
+//            short of what its range holds is redone by route A. Nothing rests on the sample but speed.
+
+static int keyed_exact(clm_index* x, const float* q32, const double* qn, int64_t nq, int k, const int32_t* keys,
+                       const int32_t* lo, const int32_t* hi, float* osc, int64_t* oix, hipStream_t st) {
+  int r = search_scan(x, true, nullptr, nullptr, q32, qn, nq, k, osc, oix, st, ScanFilter{nullptr, keys, lo, hi});
+  if (r) return r;
+  KCHK(map_ids(osc, oix, nq * k, nullptr, 0, st));
+  return CLM_OK;
+}
+
+// hn_in: the caller's counts on the host, or null; hlo / hhi: the ranges on the host
+static int keyed_pass(clm_index* x, const QueryStage& qs, int64_t nq, int k, const int32_t* keys, const int32_t* lo,
+                      const int32_t* hi, const int32_t* hlo, const int32_t* hhi, const int64_t* hn_in, int64_t S,
+                      float* osc, int64_t* oix, int64_t* n_redo, hipStream_t st) {
+  const int dim = (int)x->dim;
+  int r;
+  const int64_t ldS = round_up(S, 4) + 64;   // search_bounded's row padding
+  const int64_t nqb = band_query_block(nq, ldS * 4, 256);
+  Layout lay;
+  const size_t o_s16 = lay.take((size_t)S * dim * 2), o_si = lay.take((size_t)S * 4), o_sk = lay.take((size_t)S * 4);
+  const size_t o_sc = lay.take((size_t)nqb * ldS * 4);
+  const size_t o_ts = lay.take((size_t)nqb * k * 4), o_ti = lay.take((size_t)nqb * k * 8);
+  const size_t o_th = lay.take((size_t)nq * 4), o_cnt = lay.take((size_t)nq * 4);
+  const size_t o_cs = lay.take((size_t)nqb * CAND_CAP * 4), o_ci = lay.take((size_t)nqb * CAND_CAP * 8);
+  if ((r = grow(&x->ws2, &x->ws2_bytes, lay.total()))) return r;
+  uint8_t* w = (uint8_t*)x->ws2;
+  u16* s16 = (u16*)(w + o_s16);
+  float* sinv = (float*)(w + o_si);
+  int32_t* skeys = (int32_t*)(w + o_sk);
+  float* sc = (float*)(w + o_sc);
+  float* ts = (float*)(w + o_ts);
+  int64_t* ti = (int64_t*)(w + o_ti);
+  float* th = (float*)(w + o_th);
+  int* cnt = (int*)(w + o_cnt);
+  float* cs = (float*)(w + o_cs);
+  int64_t* ci = (int64_t*)(w + o_ci);
+  // the sample: S rows at positions floor(i * N / S) with their keys, in buffers of this call
+  KCHK(key_sample(x->rows, x->inv, keys, dim, x->n, S, s16, sinv, skeys, st));
+  if (S < k) KCHK(fill_f32(th, nq, -INFINITY, st));   // fewer sample rows than k: no threshold
+  for (int64_t q0 = 0; q0 < nq && S >= k; q0 += nqb) {
+    const int64_t nb = std::min(nqb, nq - q0);
+    GemmArgs ga{};
+    ga.A = qs.q16 + q0 * dim; ga.lda = dim; ga.W = s16; ga.ldw = dim;
+    ga.M = (int)nb; ga.N = (int)S; ga.K = dim; ga.out = sc; ga.ldo = ldS;
+    ga.rscale = qs.qinv + q0; ga.cscale = sinv;
+    KCHK(gemm(false, EPI_SCORE, ga, st));
+    KCHK(key_fill(sc, ldS, nb, S, 0, skeys, lo + q0, hi + q0, st));
+    // fewer than k open sample rows: the k-th value is a struck-out -inf, and so is theta
+    if (k <= 8 && !g_kth_radix) {
+      KCHK(kth_thresholds(sc, ldS, nb, S, k, RESCORE_MARGIN, th + q0, st));
+    } else {
+      KCHK(topk_rows(sc, ldS, nb, S, k, 0, ts, ti, k, st));
+      KCHK(filter_thresholds(ts, k, nb, k, RESCORE_MARGIN, th + q0, st));
+    }
+  }
+  HIPCHK(hipMemsetAsync(cnt, 0, (size_t)nq * 4, st));
+  const ExactRows xr = exact_rows(x);
+  for (int64_t q0 = 0; q0 < nq; q0 += nqb) {
+    const int64_t nb = std::min(nqb, nq - q0);
+    GemmArgs gf = index_pass(x, qs.q16 + q0 * dim, qs.qinv + q0, nb, th + q0, cnt + q0, ci, CAND_CAP);
+    gf.cand_s = cs;
+    gf.cbound = inv_keys_of(x, st);
+    gf.keys = keys; gf.klo = lo + q0; gf.khi = hi + q0;
+    KCHK(gemm_cfg(false, EPI_FILTER_KEYS, -1, gf, st));
+    KCHK(rescore_select(cs, ci, cnt + q0, CAND_CAP, qs.q32 + q0 * dim, qs.qn + q0, dim, xr.p, xr.f16, x->offset,
+                        RESCORE_MARGIN, nb, k, osc + q0 * k, oix + q0 * k, st));
+  }
+  std::vector<int> hcnt(nq);
+  HIPCHK(hipMemcpyAsync(hcnt.data(), cnt, (size_t)nq * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  // an overflowed list, or one short of what the range holds (NaN scores pass no threshold; without
+  // the caller's counts every list short of k): route A decides
+  std::vector<int64_t> redo;
+  for (int64_t i = 0; i < nq; ++i) {
+    const int64_t open = hlo[i] > hhi[i] ? 0 : hn_in ? hn_in[i] : x->n;
+    if (hn_in && hcnt[i] > open)
+      return fail(CLM_E_ARG, "keyed search: query " + std::to_string(i) + " lists " + std::to_string(hcnt[i]) +
+                                 " rows of its range, n_in says it holds " + std::to_string(open));
+    if (hcnt[i] > CAND_CAP || hcnt[i] < std::min<int64_t>(k, open)) redo.push_back(i);
+  }
+  *n_redo = (int64_t)redo.size();
+  return redo_subset(x, redo, {{qs.q32, x->dim * 4}, {qs.qn, 8}, {lo, 4}, {hi, 4}},
+                     {{osc, (int64_t)k * 4}, {oix, (int64_t)k * 8}}, "keyed redo", st,
+                     [&](void* const* in, void* const* out) -> int {
+                       return keyed_exact(x, (const float*)in[0], (const double*)in[1], (int64_t)redo.size(), k, keys,
+                                          (const int32_t*)in[2], (const int32_t*)in[3], (float*)out[0],
+                                          (int64_t*)out[1], st);
+                     });
+}
+
+int clm_index_search_keyed(clm_index* x, const void* q, int q_dtype, int64_t nq, int k, const int32_t* keys,
+                           const int32_t* lo, const int32_t* hi, const int64_t* n_in, int flags, float* out_scores,
+                           int64_t* out_idx, void* stream) {
+  if (!x || nq < 0 || (nq > 0 && (!q || !keys || !lo || !hi || !out_scores || !out_idx)))
+    return fail(CLM_E_ARG, "bad argument");
+  if (q_dtype != CLM_F32 && q_dtype != CLM_F16) return fail(CLM_E_ARG, "queries must be f32 or f16");
+  if (k < 1 || k > 1024) return fail(CLM_E_ARG, "keyed search: 1 <= k <= 1024");
+  if (flags & ~(CLM_MASK_EXACT | CLM_MASK_PASS)) return fail(CLM_E_ARG, "keyed search: flags are 0, CLM_MASK_EXACT or CLM_MASK_PASS");
+  if (x->n == 0) return fail(CLM_E_ARG, "keyed search: the index is empty");
+  if (nq == 0) return CLM_OK;
+  DeviceGuard g(x->dev);
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t N = x->n, dim = x->dim;
+  const bool o_dev = is_device_ptr(out_scores) && is_device_ptr(out_idx);
+  Layout lay;   // the results' staging when they go to the host, then the keys and the ranges
+  const size_t o_os = o_dev ? 0 : lay.take((size_t)nq * k * 4);
+  const size_t o_oi = o_dev ? 0 : lay.take((size_t)nq * k * 8);
+  const size_t o_keys = lay.take((size_t)N * 4), o_lo = lay.take((size_t)nq * 4), o_hi = lay.take((size_t)nq * 4);
+  QueryStage qs;
+  int r = stage_queries(x, q, q_dtype, nq, lay.total(), st, &qs);
+  if (r) return r;
+  float* osc = o_dev ? out_scores : (float*)(qs.extra + o_os);
+  int64_t* oix = o_dev ? out_idx : (int64_t*)(qs.extra + o_oi);
+  int32_t* dkeys = (int32_t*)(qs.extra + o_keys);
+  int32_t* dlo = (int32_t*)(qs.extra + o_lo);
+  int32_t* dhi = (int32_t*)(qs.extra + o_hi);
+  HIPCHK(copy_in(dkeys, keys, (size_t)N * 4, st));
+  HIPCHK(copy_in(dlo, lo, (size_t)nq * 4, st));
+  HIPCHK(copy_in(dhi, hi, (size_t)nq * 4, st));
+  const char* e_full = getenv("CLM_SEARCH_FULL");
+  // a zero or non-finite inverse norm: that row's scores are NaN, which only the exact route places
+  // (see search_masked). Drains the stream: the copies above are done
+  bool fin = false;
+  if ((r = inv_norms_finite(x, st, &fin))) return r;
+  const int64_t Sd = round_up(std::max<int64_t>(8192, (int64_t)k * N / 256), 256);
+  const bool pass_ok = fin && k <= 256 && dim <= MARGIN_MAX_DIM && N <= 0x7FFFFFFF;
+  bool pass = pass_ok && !(flags & CLM_MASK_EXACT);
+  if (pass && !(flags & CLM_MASK_PASS)) pass = !(e_full && atoi(e_full)) && N >= 4 * Sd;
+  if (!pass) {
+    x->search_stats[21] += nq;
+    r = keyed_exact(x, qs.q32, qs.qn, nq, k, dkeys, dlo, dhi, osc, oix, st);
+  } else {
+    // the ranges and the caller's counts on the host: what each list must hold
+    std::vector<int32_t> hlo(nq), hhi(nq);
+    std::vector<int64_t> hn;
+    HIPCHK(hipMemcpyAsync(hlo.data(), dlo, (size_t)nq * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(hhi.data(), dhi, (size_t)nq * 4, hipMemcpyDeviceToHost, st));
+    if (n_in) {
+      hn.resize(nq);
+      if (is_device_ptr(n_in)) HIPCHK(hipMemcpyAsync(hn.data(), n_in, (size_t)nq * 8, hipMemcpyDeviceToHost, st));
+      else std::memcpy(hn.data(), n_in, (size_t)nq * 8);
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    if ((r = stage_queries_f16(x, qs, nq, st))) return r;
+    int64_t n_redo = 0;
+    r = keyed_pass(x, qs, nq, k, dkeys, dlo, dhi, hlo.data(), hhi.data(), n_in ? hn.data() : nullptr,
+                   std::min(std::min<int64_t>(Sd, 1 << 18), N), osc, oix, &n_redo, st);
+    if (!r) {
+      x->search_stats[20] += nq - n_redo;
+      x->search_stats[21] += n_redo;
+    }
+  }
+  if (r) return r;
+  if (!o_dev) {
+    HIPCHK(copy_out(out_scores, osc, (size_t)nq * k * 4, st));
+    HIPCHK(copy_out(out_idx, oix, (size_t)nq * k * 8, st));
+  }
+  HIPCHK(hipStreamSynchronize(st));   // workspaces are reused by the next call
   return CLM_OK;
 }
 

@@ -54,36 +54,38 @@ __device__ __forceinline__ void lds_barrier() {
   asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
 
-// The selecting epilogues (epi_selects: FILTER / FILTER_MASK / RANK / LSE), the part the vector
+// The selecting epilogues (epi_selects: FILTER / FILTER_MASK / FILTER_KEYS / RANK / LSE), the part the vector
 // loop of epilogue() and the ragged-N path share: one row's edges and per-lane totals, the decision
-// on one score, and the row's finish. th = the row's theta: FILTER / FILTER_MASK's threshold,
-// RANK's target score t, LSE's head floor.
+// on one score, and the row's finish. th = the row's theta: FILTER / FILTER_MASK / FILTER_KEYS's
+// threshold, RANK's target score t, LSE's head floor. klo / khi (FILTER_KEYS): the row's key range.
 struct SelectRow {
   int m;
   float th, lo, hi;   // lo: the lower edge of what is listed; hi (RANK): above it a score is counted
   unsigned up;        // RANK: this lane's scores above hi
   float sum;          // LSE: this lane's tail terms
 };
+constexpr bool epi_filters(int e) { return e == EPI_FILTER || e == EPI_FILTER_MASK || e == EPI_FILTER_KEYS; }
 template <int EPI>
 __device__ __forceinline__ SelectRow select_row(const GemmArgs& g, int m, float th) {
   constexpr bool BAND = EPI == EPI_RANK || EPI == EPI_LSE;   // they list a band of undecided rows from theta - margin up
   return SelectRow{m, th, BAND ? th - g.rank_margin : th, th + g.rank_margin, 0u, 0.f};
 }
-// Score sc of column n, whose mask bit is `open` (FILTER_MASK; a closed column is not tested).
+// Score sc of column n, which is `open` to the row or not (FILTER_MASK: its mask bit; FILTER_KEYS: its
+// key lies in the row's range; a closed column is not tested).
 // At or above lo it takes a slot of the row's list from cnt (counted past cap, stored below it):
-// FILTER / FILTER_MASK store the score and the id, RANK / LSE the id alone. RANK counts a score
+// the FILTER family stores the score and the id, RANK / LSE the id alone. RANK counts a score
 // above hi instead (certainly ahead of the target) and drops one below lo; LSE adds one below lo to
 // the tail as exp2((s - theta) * c), c = scale * log2(e), a term below 1: no running maximum. A NaN
 // score fails every comparison: dropped, and in LSE it makes the tail NaN.
 template <int EPI>
 __device__ __forceinline__ void select_one(const GemmArgs& g, SelectRow& r, int n, bool open, float sc) {
-  if (EPI == EPI_FILTER_MASK && !open) return;
+  if ((EPI == EPI_FILTER_MASK || EPI == EPI_FILTER_KEYS) && !open) return;
   if (EPI == EPI_RANK && sc > r.hi) {
     ++r.up;
   } else if (sc >= r.lo) {
     const int slot = atomicAdd(g.cnt + r.m, 1);
     if (slot < g.cap) {
-      if constexpr (EPI == EPI_FILTER || EPI == EPI_FILTER_MASK) g.cand_s[(int64_t)r.m * g.cap + slot] = sc;
+      if constexpr (epi_filters(EPI)) g.cand_s[(int64_t)r.m * g.cap + slot] = sc;
       g.cand_i[(int64_t)r.m * g.cap + slot] = g.base + n;
     }
   } else if (EPI == EPI_LSE) {
@@ -123,6 +125,8 @@ __device__ __forceinline__ void epilogue_scalar(const GemmArgs& g, const f32x4 (
     if (m >= g.M) continue;
     const float rs = (EPI == EPI_SCORE || epi_selects(EPI)) && g.rscale ? g.rscale[m] : 1.f;
     SelectRow sel = select_row<EPI>(g, m, epi_selects(EPI) ? g.theta[(int64_t)m * g.theta_ld] : 0.f);
+    int klo = 0, khi = 0;   // FILTER_KEYS: the row's key range
+    if constexpr (EPI == EPI_FILTER_KEYS) { klo = g.klo[m]; khi = g.khi[m]; }
     int64_t prow = m;
     const float* aux = nullptr;
     if constexpr (EPI == EPI_PATCH) {
@@ -150,7 +154,9 @@ __device__ __forceinline__ void epilogue_scalar(const GemmArgs& g, const f32x4 (
         }
         else {
           static_assert(epi_selects(EPI), "unknown epilogue");
-          const bool open = EPI != EPI_FILTER_MASK || ((g.mask[nj >> 5] >> (nj & 31)) & 1u);
+          bool open = true;
+          if constexpr (EPI == EPI_FILTER_MASK) open = (g.mask[nj >> 5] >> (nj & 31)) & 1u;
+          if constexpr (EPI == EPI_FILTER_KEYS) open = klo <= g.keys[nj] && g.keys[nj] <= khi;
           select_one<EPI>(g, sel, nj, open, x * rs * g.cscale[nj]);
         }
       }
@@ -344,21 +350,31 @@ __device__ __forceinline__ void epilogue(const GemmArgs& g, const f32x4 (&acc)[B
     }
   } else {   // EPI_SCORE and the selecting epilogues: score = dot * rscale[m] * cscale[n], in this order
     float rs[C::TM], th[C::TM];
+    int klo[EPI == EPI_FILTER_KEYS ? C::TM : 1] = {}, khi[EPI == EPI_FILTER_KEYS ? C::TM : 1] = {};   // the rows' key ranges
 #pragma unroll
     for (int mb = 0; mb < C::TM; ++mb) {
       const int m = wrow + mb * 16;
       rs[mb] = (g.rscale && m < g.M) ? g.rscale[m] : 1.f;
       if constexpr (epi_selects(EPI)) th[mb] = m < g.M ? g.theta[(int64_t)m * g.theta_ld] : 0.f;
+      if constexpr (EPI == EPI_FILTER_KEYS) {   // a row past M gets the empty range
+        klo[mb] = m < g.M ? g.klo[m] : 1;
+        khi[mb] = m < g.M ? g.khi[m] : 0;
+      }
     }
     if constexpr (epi_selects(EPI)) {
-      // One loop over the row blocks and their 16 x 16 blocks for FILTER / FILTER_MASK / RANK / LSE.
+      // One loop over the row blocks and their 16 x 16 blocks for FILTER / FILTER_MASK / FILTER_KEYS /
+      // RANK / LSE.
       // What differs between them is compile-time: the lower edge and what a score does on either
       // side of it (select_row / select_one), the row's finish (select_finish), FILTER_MASK's bits
       // and whether there is a skip test. LSE has none: every row contributes to its tail sum.
-      constexpr bool MASKED = EPI == EPI_FILTER_MASK, SKIP = EPI != EPI_LSE;
+      constexpr bool MASKED = EPI == EPI_FILTER_MASK, KEYED = EPI == EPI_FILTER_KEYS, SKIP = EPI != EPI_LSE;
       // FILTER_MASK: the lane's 4 columns n .. n + 3 (n % 4 == 0) are one nibble of word n >> 5,
       // which never straddles a word; the nibbles do not depend on the row block, so they are read
       // once per tile (the words of a tile: BN / 8 bytes, L2-resident). The others: all four open.
+      // FILTER_KEYS' open test depends on the row as well: it is no part of nib or of the skip test
+      // (which runs as FILTER's does); the nibble of a (row, block) that survives is built from the
+      // lane's 4 keys, one 16-byte load beside the cscale load, and a row whose range is empty
+      // (klo > khi) is not live.
       unsigned nib[C::TN], any_bits = 0;
 #pragma unroll
       for (int nb = 0; nb < C::TN; ++nb) {
@@ -387,7 +403,7 @@ __device__ __forceinline__ void epilogue(const GemmArgs& g, const f32x4 (&acc)[B
 #pragma unroll
       for (int mb = 0; mb < C::TM; ++mb) {
         SelectRow r = select_row<EPI>(g, wrow + mb * 16, th[mb]);
-        const bool live = r.m < g.M;
+        const bool live = r.m < g.M && (!KEYED || klo[KEYED ? mb : 0] <= khi[KEYED ? mb : 0]);
         const bool rok = cok && rs[mb] >= 0.f && rs[mb] <= 3.4028235e38f && r.lo >= -3.4028235e38f;
         auto reach = [&](float v) { return live && (!rok || (v * rs[mb]) * (v >= 0.f ? cmax : cmin) >= r.lo); };
         float bmx[C::TN];
@@ -407,10 +423,17 @@ __device__ __forceinline__ void epilogue(const GemmArgs& g, const f32x4 (&acc)[B
           const int n = wcol + nb * 16;
           if (!live || (MASKED ? !nib[nb] : n >= g.N)) continue;   // a set bit implies n < N
           const float4 c = g.cscale ? *(const float4*)(g.cscale + n) : make_float4(1.f, 1.f, 1.f, 1.f);
+          unsigned open = nib[nb];
+          if constexpr (KEYED) {
+            const int4 kk = *(const int4*)(g.keys + n);
+            const int lo = klo[mb], hi = khi[mb];
+            open = (unsigned)(lo <= kk.x && kk.x <= hi) | (unsigned)(lo <= kk.y && kk.y <= hi) << 1 |
+                   (unsigned)(lo <= kk.z && kk.z <= hi) << 2 | (unsigned)(lo <= kk.w && kk.w <= hi) << 3;
+          }
           const float sc[4] = {acc[mb][nb][0] * rs[mb] * c.x, acc[mb][nb][1] * rs[mb] * c.y,
                                acc[mb][nb][2] * rs[mb] * c.z, acc[mb][nb][3] * rs[mb] * c.w};
 #pragma unroll
-          for (int j = 0; j < 4; ++j) select_one<EPI>(g, r, n + j, (nib[nb] >> j) & 1u, sc[j]);
+          for (int j = 0; j < 4; ++j) select_one<EPI>(g, r, n + j, (open >> j) & 1u, sc[j]);
         }
         select_finish<EPI>(g, r, live, lane, slot);
       }

@@ -65,6 +65,8 @@ static void argument_checks() {
   CHECK(clm_index_size(nullptr) < 0);
   CHECK(clm_index_search(nullptr, nullptr, CLM_F32, 1, 1, nullptr, nullptr, nullptr) != CLM_OK);
   CHECK(clm_index_search_masked(nullptr, nullptr, CLM_F32, 1, 1, nullptr, 0, nullptr, nullptr, nullptr) == CLM_E_ARG);
+  CHECK(clm_index_search_keyed(nullptr, nullptr, CLM_F32, 1, 1, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr,
+                               nullptr) == CLM_E_ARG);
   int64_t st[4];
   CHECK(clm_index_stats2(nullptr, st, 4) != CLM_OK);
   CHECK(clm_gemm(0, 99, CLM_EPI_STORE, -1, nullptr, 64, nullptr, 64, 1, 1, 64, nullptr, 1, nullptr, nullptr, nullptr,
@@ -249,6 +251,27 @@ static void argument_checks() {
         CHECK(sel(CLM_EPI_RANK, cfg, x, 128, x, 128, 1, 8, 128, f, f, 1, one, nullptr, ci, 1, u, f, 4, u) == CLM_E_HIP);
         CHECK(sel(CLM_EPI_LSE, cfg, x, 128, x, 128, 1, 8, 128, f, f, 1, one, nullptr, ci, 1, u, f, 4, u) == CLM_E_HIP);
         CHECK(sel(CLM_EPI_FILTER_MASK, cfg, x, 128, x, 128, 1, 8, 128, f, f, 1, one, f, ci, 1, u, f, 4, u) == CLM_E_HIP);
+      }
+      {   // clm_gemm_select_keyed(dev, config, A, lda, W, ldw, M, N, K, rscale, cscale, theta, theta_ld, cnt, cand_s,
+          //                       cand_i, cap, base, cbound, keys, klo, khi, m_fastest, stream)
+        alignas(16) int32_t kk[4] = {0, 1, 2, 3};
+        int32_t kr[1] = {0};
+        auto keyed = [&](int cfg, const void* A, int64_t lda, int M, int N, int K, float* cand_s, int cap,
+                         const int32_t* keys, const int32_t* klo, const int32_t* khi) {
+          return clm_gemm_select_keyed(0, cfg, A, lda, x, 64, M, N, K, nullptr, f, f, 1, one, cand_s, ci, cap, 0, nullptr,
+                                       keys, klo, khi, 1, nullptr);
+        };
+        CHECK(keyed(99, x, 64, 1, 1, 64, f, 1, kk, kr, kr) == CLM_E_ARG);        // config
+        CHECK(keyed(-1, x, 64, -1, 1, 64, f, 1, kk, kr, kr) == CLM_E_ARG);       // M < 0
+        CHECK(keyed(-1, x, 96, 1, 1, 96, f, 1, kk, kr, kr) == CLM_E_ARG);        // K % 64
+        CHECK(keyed(-1, x, 64, 1, 1, 64, f, 0, kk, kr, kr) == CLM_E_ARG);        // cap < 1
+        CHECK(keyed(-1, nullptr, 64, 1, 1, 64, f, 1, kk, kr, kr) == CLM_E_ARG);  // A
+        CHECK(keyed(-1, x, 64, 1, 1, 64, nullptr, 1, kk, kr, kr) == CLM_E_ARG);  // cand_s
+        CHECK(keyed(-1, x, 64, 1, 1, 64, f, 1, nullptr, kr, kr) == CLM_E_ARG);   // keys
+        CHECK(keyed(-1, x, 64, 1, 1, 64, f, 1, kk + 1, kr, kr) == CLM_E_ARG);    // ... 16-byte aligned
+        CHECK(keyed(-1, x, 64, 1, 1, 64, f, 1, kk, nullptr, kr) == CLM_E_ARG);   // klo
+        CHECK(keyed(-1, x, 64, 1, 1, 64, f, 1, kk, kr, nullptr) == CLM_E_ARG);   // khi
+        CHECK(keyed(-1, nullptr, 64, 0, 4, 64, nullptr, 1, nullptr, nullptr, nullptr) == CLM_OK);   // M == 0
       }
       // nothing to do: M == 0 or N == 0, whatever the pointers
       CHECK(sel(CLM_EPI_FILTER, -1, nullptr, 64, nullptr, 64, 0, 4, 64, nullptr, nullptr, 1, nullptr, nullptr, nullptr, 1,
@@ -532,6 +555,56 @@ static void device_checks() {
     CHECK(clm_index_search_masked(idx, q.data(), CLM_BF16, nq, k, allow.data(), 0, sc.data(), ix.data(), nullptr) == CLM_E_ARG);
     CHECK(clm_index_search_masked(idx, q.data(), CLM_F32, nq, 0, allow.data(), 0, sc.data(), ix.data(), nullptr) == CLM_E_ARG);
   }
+  {   // keyed search on host buffers: key = row number mod 7, one range per query (query 1's empty), both
+      // routes, against the host reference over each query's open rows; then what the entry point refuses
+    std::vector<int32_t> keys(n), lo(nq), hi(nq);
+    std::vector<int64_t> n_in(nq, 0);
+    for (int j = 0; j < n; ++j) keys[j] = j % 7;
+    for (int i = 0; i < nq; ++i) {
+      lo[i] = i % 4;
+      hi[i] = i == 1 ? -1 : i % 4 + i % 3;
+      for (int j = 0; j < n; ++j) n_in[i] += lo[i] <= keys[j] && keys[j] <= hi[i];
+    }
+    for (int flag : {0, (int)CLM_MASK_EXACT, (int)CLM_MASK_PASS}) {
+      for (const int64_t* counts : {(const int64_t*)n_in.data(), (const int64_t*)nullptr}) {
+        CHECK(clm_index_search_keyed(idx, q.data(), CLM_F32, nq, k, keys.data(), lo.data(), hi.data(), counts, flag,
+                                     sc.data(), ix.data(), nullptr) == CLM_OK);
+        for (int i = 0; i < nq; ++i) {
+          std::vector<std::pair<double, int64_t>> all;
+          for (int j = 0; j < n; ++j)
+            if (lo[i] <= keys[j] && keys[j] <= hi[i]) all.push_back({cos64(&q[(size_t)i * dim], &rows[(size_t)j * dim], dim), j});
+          std::sort(all.begin(), all.end(), [](const auto& a, const auto& b) {
+            return a.first > b.first || (a.first == b.first && a.second < b.second);
+          });
+          for (int t = 0; t < k; ++t) {
+            if (t < (int)all.size()) CHECK(ix[(size_t)i * k + t] == all[t].second && sc[(size_t)i * k + t] == (float)all[t].first);
+            else CHECK(ix[(size_t)i * k + t] == -1);
+          }
+        }
+      }
+    }
+    int64_t ks[22] = {0};
+    CHECK(clm_index_stats2(idx, ks, 22) == CLM_OK && ks[20] + ks[21] == 6 * (int64_t)nq);
+    auto keyed = [&](const void* qq, int dt, int64_t m, int kk, const int32_t* ky, const int32_t* l, const int32_t* h,
+                     int flag, float* os) {
+      return clm_index_search_keyed(idx, qq, dt, m, kk, ky, l, h, nullptr, flag, os, ix.data(), nullptr);
+    };
+    CHECK(keyed(nullptr, CLM_F32, nq, k, keys.data(), lo.data(), hi.data(), 0, sc.data()) == CLM_E_ARG);
+    CHECK(keyed(q.data(), CLM_F32, nq, k, nullptr, lo.data(), hi.data(), 0, sc.data()) == CLM_E_ARG);
+    CHECK(keyed(q.data(), CLM_F32, nq, k, keys.data(), nullptr, hi.data(), 0, sc.data()) == CLM_E_ARG);
+    CHECK(keyed(q.data(), CLM_F32, nq, k, keys.data(), lo.data(), nullptr, 0, sc.data()) == CLM_E_ARG);
+    CHECK(keyed(q.data(), CLM_F32, nq, k, keys.data(), lo.data(), hi.data(), 0, nullptr) == CLM_E_ARG);
+    CHECK(keyed(q.data(), CLM_BF16, nq, k, keys.data(), lo.data(), hi.data(), 0, sc.data()) == CLM_E_ARG);
+    CHECK(keyed(q.data(), CLM_F32, -1, k, keys.data(), lo.data(), hi.data(), 0, sc.data()) == CLM_E_ARG);
+    CHECK(keyed(q.data(), CLM_F32, nq, 0, keys.data(), lo.data(), hi.data(), 0, sc.data()) == CLM_E_ARG);
+    CHECK(keyed(q.data(), CLM_F32, nq, 1025, keys.data(), lo.data(), hi.data(), 0, sc.data()) == CLM_E_ARG);
+    CHECK(keyed(q.data(), CLM_F32, nq, k, keys.data(), lo.data(), hi.data(), CLM_MASK_GATHER, sc.data()) == CLM_E_ARG);
+    CHECK(keyed(q.data(), CLM_F32, nq, k, keys.data(), lo.data(), hi.data(), 1, sc.data()) == CLM_E_ARG);   // an unknown flag
+    CHECK(keyed(nullptr, CLM_F32, 0, k, nullptr, nullptr, nullptr, 0, nullptr) == CLM_OK);                  // nq == 0
+    std::vector<int64_t> wrong(nq, 0);   // counts that say every range is empty: the pass route sees more
+    CHECK(clm_index_search_keyed(idx, q.data(), CLM_F32, nq, k, keys.data(), lo.data(), hi.data(), wrong.data(),
+                                 CLM_MASK_PASS, sc.data(), ix.data(), nullptr) == CLM_E_ARG);
+  }
   CHECK(clm_index_set_offset(idx, 1000) == CLM_OK);
   CHECK(clm_index_search(idx, q.data(), CLM_F32, 1, 1, sc.data(), ix.data(), nullptr) == CLM_OK);
   CHECK(ix[0] >= 1000);
@@ -621,6 +694,11 @@ static void device_checks() {
   CHECK(clm_index_lse(idx, q.data(), CLM_F32, 1, 100.0, nullptr, &st_lse, nullptr, 0, nullptr) == CLM_E_ARG);   // empty
   CHECK(clm_index_search(idx, q.data(), CLM_F32, nq, 3, sc.data(), ix.data(), nullptr) == CLM_OK);
   CHECK(ix[0] == -1 && std::isinf(sc[0]));   // empty index: (-inf, -1) slots
+  {   // ... which the keyed search refuses
+    int32_t k0 = 0;
+    CHECK(clm_index_search_keyed(idx, q.data(), CLM_F32, 1, 3, &k0, &k0, &k0, nullptr, 0, sc.data(), ix.data(),
+                                 nullptr) == CLM_E_ARG);
+  }
   {   // ... which has no ranks
     int64_t t0 = 1000, r0 = 0;
     float s0 = 0.f;

@@ -353,12 +353,13 @@ int pick_config(int epi, int M, int N) {
   return pick_from(MODELS_G2, M, N);
 }
 
-// RANK / LSE / FILTER_MASK: fp16, on the tiles the filter pass runs on (config 1 and G2's 8-11);
-// FILTER_MASK requires the mask words
+// RANK / LSE / FILTER_MASK / FILTER_KEYS: fp16, on the tiles the filter pass runs on (config 1 and
+// G2's 8-11); FILTER_MASK requires the mask words, FILTER_KEYS the keys and both range arrays
 template <bool BF, int EPI>
 hipError_t launch_fp16_select(int id, const GemmArgs& g, hipStream_t s) {
   if constexpr (!BF) {
     if (EPI == EPI_FILTER_MASK && !g.mask) return hipErrorInvalidValue;
+    if (EPI == EPI_FILTER_KEYS && (!g.keys || !g.klo || !g.khi)) return hipErrorInvalidValue;
     if (id == 1) return launch_cfg<false, EPI, 256, 256, 4, 2, 2>(g, s);
     if (id >= 8 && id <= 11) return gemm2_launch(false, EPI, id, g, s);
   }
@@ -377,6 +378,7 @@ hipError_t dispatch(int epi, int id, const GemmArgs& g, hipStream_t s) {
     case EPI_RANK: return launch_fp16_select<BF, EPI_RANK>(id, g, s);
     case EPI_LSE: return launch_fp16_select<BF, EPI_LSE>(id, g, s);
     case EPI_FILTER_MASK: return launch_fp16_select<BF, EPI_FILTER_MASK>(id, g, s);
+    case EPI_FILTER_KEYS: return launch_fp16_select<BF, EPI_FILTER_KEYS>(id, g, s);
     default: return hipErrorInvalidValue;
   }
 }

@@ -235,6 +235,7 @@ hipError_t by_epi(int epi, int id, const GemmArgs& g, hipStream_t s) {
     case EPI_RANK: return by_id_fp16<BF, EPI_RANK>(id, g, s);
     case EPI_LSE: return by_id_fp16<BF, EPI_LSE>(id, g, s);
     case EPI_FILTER_MASK: return by_id_fp16<BF, EPI_FILTER_MASK>(id, g, s);
+    case EPI_FILTER_KEYS: return by_id_fp16<BF, EPI_FILTER_KEYS>(id, g, s);
     default: return hipErrorInvalidValue;
   }
 }

@@ -27,9 +27,12 @@ enum Epi {
                    // (column tile) * (wave columns of the config) + wave column < lse_slots(N): every
                    // slot a config uses is written once per live row, the others keep the caller's
                    // zeros. fp16, configs 1 and 8-11 only
-  EPI_FILTER_MASK = 8     // EPI_FILTER over the rows a bitset allows: column n is tested only where
+  EPI_FILTER_MASK = 8,    // EPI_FILTER over the rows a bitset allows: column n is tested only where
                           // bit n & 31 of mask[n >> 5] is set (bits at or past N clear:
                           // mask_prepare). fp16, configs 1 and 8-11 only
+  EPI_FILTER_KEYS = 9     // EPI_FILTER with one open test per (row, column): column n is tested for row m
+                          // only where klo[m] <= keys[n] <= khi[m] (a row with klo > khi lists nothing).
+                          // fp16, configs 1 and 8-11 only
 };
 // upper bound, over the configs EPI_LSE runs on, of the slab slots per row (wave column extents are
 // 64, 96 or 128 index rows)
@@ -38,7 +41,7 @@ constexpr bool epi_stores16(int e) { return e == EPI_STORE || e == EPI_GELU; }
 constexpr bool epi_gelu(int e) { return e == EPI_GELU; }
 // the index passes' selecting epilogues: they compare each score with theta[m] and append / count / sum
 constexpr bool epi_selects(int e) {
-  return e == EPI_FILTER || e == EPI_FILTER_MASK || e == EPI_RANK || e == EPI_LSE;
+  return e == EPI_FILTER || e == EPI_FILTER_MASK || e == EPI_FILTER_KEYS || e == EPI_RANK || e == EPI_LSE;
 }
 
 struct GemmArgs {
@@ -74,6 +77,9 @@ struct GemmArgs {
   float* lse_part; int64_t lse_ld; float lse_c;
   // EPI_FILTER_MASK (with the EPI_FILTER fields): ceil(N / 32) words, read by that epilogue only
   const uint32_t* mask;
+  // EPI_FILTER_KEYS (with the EPI_FILTER fields): keys [N], one per column (16-byte aligned: the
+  // vector epilogue loads a lane's 4 at once); klo / khi [M], the row's inclusive key range
+  const int32_t* keys; const int32_t* klo; const int32_t* khi;
 };
 
 hipError_t gemm(bool bf16, int epi, const GemmArgs& g, hipStream_t s);
@@ -435,6 +441,16 @@ hipError_t map_ids(const float* scores, int64_t* ids, int64_t n, const uint32_t*
 // order): fp16 rows, inverse norms, and the fp32 rows where rows32 / out32 are given; dim % 8 == 0
 hipError_t mask_gather(const u16* rows16, const float* rows32, const float* inv, int dim, const uint32_t* list,
                        int64_t P, int64_t S, u16* out16, float* out32, float* out_inv, hipStream_t s);
+// ---- keyed search (k_keys.hip): one int32 key per index row, one inclusive key range per query
+// mask_fill with the per-query predicate: scores [nq, C] (row stride lds), column j = local row
+// r0 + j: -inf where keys[r0 + j] lies outside [lo[y], hi[y]] of query y; a NaN inside gets its sign
+// bit cleared
+hipError_t key_fill(float* scores, int64_t lds, int64_t nq, int64_t C, int64_t r0, const int32_t* keys,
+                    const int32_t* lo, const int32_t* hi, hipStream_t s);
+// the strided sample: out row i = row floor(i * N / S) of the index's arrays (S <= N): fp16 row,
+// inverse norm and key; dim % 8 == 0
+hipError_t key_sample(const u16* rows16, const float* inv, const int32_t* keys, int dim, int64_t N, int64_t S,
+                      u16* out16, float* out_inv, int32_t* out_keys, hipStream_t s);
 // out[i] = value for i < n (floats)
 hipError_t fill_f32(float* out, int64_t n, float value, hipStream_t s);
 

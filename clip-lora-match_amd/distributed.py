@@ -282,6 +282,40 @@ class ShardedIndex:
         s_all, i_all = gather_candidates(s, i, self.group)
         return merge(s_all, i_all, self.world, k)
 
+    def search_where(self, queries: torch.Tensor, k: int, values, lo, hi, allow=None,
+                     merge: Callable = merge_topk_gpu) -> Tuple[torch.Tensor, torch.Tensor]:
+        """CosineIndex.search_where over the whole sharded index (a collective call): one inclusive value
+        range per query. values: one number per row of the WHOLE index [n_total], the same on every rank;
+        lo / hi: as CosineIndex.search_where takes them; allow: as in `search`. The ranks are planned on
+        the full values (key_ranks), so every shard reads the bounds alike; each rank searches its slice of
+        the keys and the lists merge as `search`'s do. A shard without rows contributes (-inf, -1) lists."""
+        from .search import KeyPlan, _allowed_rows, key_ranks
+        v = torch.as_tensor(values).reshape(-1)
+        if v.numel() != self.n_total:
+            raise ValueError(f"values must hold one number per row of the whole index ({self.n_total}), got {v.numel()}")
+        keep = None
+        if allow is not None:
+            a = torch.as_tensor(allow)
+            keep = _allowed_rows(self.n_total, 0, keep=a) if a.dtype == torch.bool else \
+                _allowed_rows(self.n_total, 0, ids=a)
+        dev = getattr(self.local, "device", "cpu")
+        if len(self.local) == 0:   # an empty index refuses the call
+            nq = 1 if torch.as_tensor(queries).dim() == 1 else torch.as_tensor(queries).shape[0]
+            s = torch.full((nq, k), float("-inf"), dtype=torch.float32, device=dev)
+            i = torch.full((nq, k), -1, dtype=torch.int64, device=dev)
+        else:
+            keys, uniq, _ = key_ranks(v, keep)
+            mine = keys[self.start: self.stop].to(dev).contiguous()
+            # the shard's own prefix counts: what its lists must hold
+            cum = torch.zeros((uniq.numel() + 1,), dtype=torch.int64, device=dev)
+            cum[1:] = torch.cumsum(torch.bincount(mine[mine >= 0].to(torch.int64), minlength=uniq.numel()), 0)
+            plan = KeyPlan(mine, uniq.to(dev), cum, self.stop - self.start)
+            s, i = self.local.search_where(queries, k, plan, lo, hi)
+        if self.world == 1:
+            return s, i
+        s_all, i_all = gather_candidates(s, i, self.group)
+        return merge(s_all, i_all, self.world, k)
+
     def search_grouped(self, queries: torch.Tensor, k: int, groups, allow=None,
                        merge: Callable = merge_grouped_gpu) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """CosineIndex.search_grouped over the whole sharded index (a collective call): (scores, idx,

@@ -26,7 +26,7 @@ from typing import Dict, List, Optional, Sequence, Union
 import torch
 
 from .clip_model import encode_text
-from .search import TextSearchIndex
+from .search import SearchResult, TextSearchIndex
 
 PathLike = Union[str, Path]
 
@@ -210,6 +210,22 @@ class FinderIndex:
         if where is None:
             return self.index.search_with_embedding(query_emb, top_k=top_k)
         return self.index.search_with_embedding(query_emb, top_k=top_k, allow=where)
+
+    def search_many(self, query_embs, top_k: int, keys, lo, hi) -> List[List[SearchResult]]:
+        """Many seekers in one batched search, each with its own inclusive value range over the items:
+        query i sees the items with lo[i] <= keys[j] <= hi[i] (keys: one number per item -- a found_at
+        timestamp, a location or category code --, a callable (i, image_path, text) -> number, or a
+        CosineIndex.key_plan(); lo / hi: [nq], a scalar, or None for an open side;
+        TextSearchIndex.search_batch's keys=). One SearchResult list per query, best first, shorter than
+        top_k where fewer items lie in its range."""
+        scores, indices = self.index.search_batch(query_embs, top_k, keys=keys, lo=lo, hi=hi)
+        paths, texts = self.index.image_paths, self.index.texts
+        out: List[List[SearchResult]] = []
+        for row_i, row_s in zip(indices.tolist(), scores.tolist()):
+            out.append([SearchResult(index=j, score=float(sc), image_path=paths[j] if j < len(paths) else "",
+                                     text=texts[j] if j < len(texts) else "")
+                        for j, sc in zip(row_i, row_s) if j >= 0])
+        return out
 
 
 __all__ = ["FinderIndex"]

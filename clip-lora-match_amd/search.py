@@ -33,6 +33,7 @@ from __future__ import annotations
 
 import ctypes
 import json
+import math
 import struct
 from dataclasses import dataclass
 from pathlib import Path
@@ -105,6 +106,92 @@ def group_ids_from_keys(keys) -> torch.Tensor:
     """hashable keys [N] -> dense int64 group ids [N], numbered by first occurrence (CPU)"""
     seen: dict = {}
     return torch.tensor([seen.setdefault(key, len(seen)) for key in keys], dtype=torch.int64)
+
+
+def key_ranks(values, allow=None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """values [N] (any integer or floating dtype, no NaN) -> (keys int32 [N], uniq [U], cum int64 [U + 1]):
+    uniq = the sorted distinct values, keys[j] = the rank of values[j] among them -- or -1, which no range
+    of key_bounds holds, where allow (bool [N]) excludes row j: a batch-wide filter rides on the keys --,
+    cum[r] = the allowed rows of rank < r. Torch ops on values' device."""
+    if not isinstance(values, torch.Tensor):   # Python floats at their own precision (float64)
+        values = np.asarray(values)
+    v = torch.as_tensor(values).reshape(-1)
+    if v.dtype == torch.bool:
+        v = v.to(torch.int64)
+    if v.is_complex():
+        raise TypeError("key values must be integers or floats")
+    if v.is_floating_point() and bool(torch.isnan(v).any()):
+        raise ValueError("key values must not hold NaN: a NaN has no rank")
+    uniq, inv = torch.unique(v, sorted=True, return_inverse=True)
+    keys = inv.to(torch.int32)
+    if allow is not None:
+        keep = torch.as_tensor(allow).reshape(-1)
+        if keep.dtype != torch.bool or keep.numel() != v.numel():
+            raise ValueError(f"allow must be a bool tensor of {v.numel()} rows, got {keep.dtype} x {keep.numel()}")
+        keep = keep.to(v.device)
+        keys = torch.where(keep, keys, torch.full_like(keys, -1))
+        inv = inv[keep]
+    cum = torch.zeros((uniq.numel() + 1,), dtype=torch.int64, device=v.device)
+    cum[1:] = torch.cumsum(torch.bincount(inv, minlength=uniq.numel()), 0)
+    return keys, uniq, cum
+
+
+def _key_edge(uniq: torch.Tensor, bound, nq: Optional[int], lower: bool) -> torch.Tensor:
+    """one side of key_bounds: the bound values [nq] (a scalar broadcasts, None = open) -> the first rank
+    inside (lower) or the last rank inside (upper), int64 on uniq's device"""
+    U = uniq.numel()
+    if bound is None:
+        bound = -math.inf if lower else math.inf
+    if not isinstance(bound, torch.Tensor):   # Python floats at their own precision (float64), not torch's float32
+        bound = np.asarray(bound)
+    b = torch.as_tensor(bound).reshape(-1).to(uniq.device)
+    if b.dtype == torch.bool or b.is_complex():
+        raise TypeError("key bounds must be integers or floats")
+    if b.is_floating_point() and bool(torch.isnan(b).any()):
+        raise ValueError("a key bound is NaN")
+    if nq is not None and b.numel() not in (1, nq):
+        raise ValueError(f"key bounds: {b.numel()} values for {nq} queries")
+    if b.is_floating_point() and not uniq.is_floating_point():
+        # integer values against a fractional or infinite bound: the nearest integer inside, clamped to
+        # what int64 holds (a bound beyond it lies beyond every value)
+        lim = float(2 ** 62)
+        b = (torch.ceil(b.double()) if lower else torch.floor(b.double())).clamp(-lim, lim).to(torch.int64)
+        u = uniq.to(torch.int64).clamp(-(2 ** 62) + 1, 2 ** 62 - 1)
+    elif uniq.is_floating_point() or b.is_floating_point():
+        b, u = b.double(), uniq.double()
+    else:
+        b, u = b.to(torch.int64), uniq.to(torch.int64)
+    r = torch.searchsorted(u, b, right=not lower) if U else torch.zeros_like(b, dtype=torch.int64)
+    r = r if lower else r - 1
+    return r.expand(nq).contiguous() if nq is not None and r.numel() == 1 else r
+
+
+def key_bounds(uniq, cum, lo, hi, nq: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Per-query value bounds, inclusive, -> (klo int32 [nq], khi int32 [nq], n_in int64 [nq]) over the
+    ranks of key_ranks: klo = the first rank with uniq >= lo, khi = the last with uniq <= hi (klo > khi: no
+    value lies inside), n_in = the allowed rows inside. lo / hi: [nq] values, a scalar (every query), or
+    None / -inf / +inf for an open side; nq (optional) is what two scalars broadcast to."""
+    uniq, cum = torch.as_tensor(uniq), torch.as_tensor(cum).to(torch.int64)
+    klo, khi = _key_edge(uniq, lo, nq, True), _key_edge(uniq, hi, nq, False)
+    if klo.numel() != khi.numel():
+        n = max(klo.numel(), khi.numel())
+        if min(klo.numel(), khi.numel()) != 1:
+            raise ValueError(f"key bounds: {klo.numel()} lower vs {khi.numel()} upper values")
+        klo, khi = klo.expand(n).contiguous(), khi.expand(n).contiguous()
+    n_in = torch.where(klo <= khi, cum[(khi + 1).clamp(0, uniq.numel())] - cum[klo.clamp(0, uniq.numel())],
+                       torch.zeros_like(klo))
+    return klo.to(torch.int32), khi.to(torch.int32), n_in
+
+
+@dataclass
+class KeyPlan:
+    """What search_where needs of the rows' key values (CosineIndex.key_plan), reusable until the index's
+    rows change: keys [N] int32 on the device (local row order; -1 = excluded by the plan's filter), the
+    sorted distinct values uniq and the prefix counts cum of key_ranks, n = the rows planned for."""
+    keys: torch.Tensor
+    uniq: torch.Tensor
+    cum: torch.Tensor
+    n: int
 
 
 GROUP_ROUTE_THRESHOLD = 1   # search_grouped(route=): every query by the threshold route
@@ -280,6 +367,58 @@ class CosineIndex:
         v = (ctypes.c_int64 * 20)()
         C.check(C.lib().clm_index_stats2(self._h, v, 20))
         return {"pass": v[17], "gather": v[18], "exact": v[19]}
+
+    # ----------------------------------------------------------- keyed search --
+    def key_plan(self, values, allow=None) -> KeyPlan:
+        """The KeyPlan of one value per row (values [N], local row order: timestamps, categories, prices
+        -- any integer or floating dtype, no NaN) and an optional batch-wide row filter (allow as `search`
+        takes it). Torch ops only; reusable across search_where calls until the index's rows change."""
+        n = len(self)
+        v = torch.as_tensor(values).reshape(-1)
+        if v.numel() != n:
+            raise ValueError(f"key values: {v.numel()} for an index of {n} rows")
+        keep = None if allow is None else unpack_mask(self._allow_words(allow), n)
+        keys, uniq, cum = key_ranks(v.to(self.device), keep)
+        return KeyPlan(keys.contiguous(), uniq, cum, n)
+
+    def search_where(self, queries, k: int, keys, lo, hi, allow=None,
+                     route: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Exact top-k under one value range PER QUERY, in one batched pass: row j competes for query i
+        iff lo[i] <= value[j] <= hi[i] (inclusive; lo / hi as key_bounds takes them: [nq], a scalar, None
+        or an infinity for an open side). keys: a key_plan(), or the values [N] themselves, planned on
+        the fly with `allow` (a batch-wide filter as `search` takes it; a KeyPlan holds its own, so allow
+        must then be None). Row i of the result is search(queries[i], k, allow=the rows in its range):
+        the same order, exact scores and ids, (-inf, -1) past the rows in range. k <= 1024. route: 0, or
+        C.CLM_MASK_EXACT / _PASS (the results do not depend on it). (clm_index_search_keyed)"""
+        if isinstance(keys, KeyPlan):
+            if allow is not None:
+                raise ValueError("search_where: a KeyPlan holds its own filter (key_plan(values, allow=)); allow must be None")
+            plan = keys
+        else:
+            plan = self.key_plan(keys, allow)
+        q = self._queries(queries)
+        nq, n = q.shape[0], len(self)
+        if plan.n != n or plan.keys.numel() != n:
+            raise ValueError(f"search_where: the key plan holds {plan.n} rows, the index {n}: plan again after the rows change")
+        klo, khi, n_in = key_bounds(plan.uniq, plan.cum, lo, hi, nq)
+        klo, khi, n_in = klo.contiguous(), khi.contiguous(), n_in.contiguous()
+        s = torch.empty((nq, k), dtype=torch.float32, device=self.device)
+        i = torch.empty((nq, k), dtype=torch.int64, device=self.device)
+        code = C.CLM_F32 if q.dtype == torch.float32 else C.CLM_F16
+        some = nq > 0
+        C.check(C.lib().clm_index_search_keyed(self._h, C.ptr(q) if some else None, code, nq, int(k),
+                                               C.ptr(plan.keys) if some else None, C.ptr(klo) if some else None,
+                                               C.ptr(khi) if some else None, C.ptr(n_in) if some else None,
+                                               int(route), C.ptr(s) if some else None, C.ptr(i) if some else None,
+                                               C.stream_of(self.device)), "clm_index_search_keyed")
+        return s, i
+
+    def where_stats(self) -> dict:
+        """keyed-search queries served by the MFMA pass route (`pass`) and by the exact route (`exact`; a
+        pass-route query redone exactly counts here)"""
+        v = (ctypes.c_int64 * 22)()
+        C.check(C.lib().clm_index_stats2(self._h, v, 22))
+        return {"pass": v[20], "exact": v[21]}
 
     # ------------------------------------------------------------------ ranks --
     def _queries(self, queries) -> torch.Tensor:
@@ -867,9 +1006,19 @@ class TextSearchIndex:
                                                  self.texts[i] if i < len(self.texts) else "") for i in range(n)])
         return torch.as_tensor(group_by)   # CosineIndex.group_plan validates length, dtype and sign
 
-    def search_batch(self, queries, top_k: int = 5, allow=None, group_by=None):
+    def key_values(self, keys):
+        """the per-row values of a keys= argument: a KeyPlan or values [num_items] as they are, or a
+        callable (i, image_path, text) -> number evaluated over the host metadata"""
+        if callable(keys):
+            return torch.tensor([keys(i, self.image_paths[i] if i < len(self.image_paths) else "",
+                                      self.texts[i] if i < len(self.texts) else "") for i in range(self.num_items)])
+        return keys
+
+    def search_batch(self, queries, top_k: int = 5, allow=None, group_by=None, keys=None, lo=None, hi=None):
         """[nq, d] queries -> (scores [nq, k], indices [nq, k]) on the GPU, k = min(top_k, num_items).
         allow: only these rows compete (see _allow); slots past their number hold (-inf, -1).
+        keys (see key_values) with lo / hi: one inclusive value range per query -- row j competes for
+        query i iff lo[i] <= keys[j] <= hi[i] (CosineIndex.search_where; top_k <= 1024, not with group_by).
         group_by (see group_ids; or a CosineIndex.group_plan(), which holds its own filter): at most one
         row per group, its best -- (scores, indices, group ids), (-inf, -1, -1) past the number of
         distinct allowed groups (CosineIndex.search_grouped; top_k <= 1024)."""
@@ -881,6 +1030,11 @@ class TextSearchIndex:
             nq = 1 if q.dim() == 1 else q.shape[0]
             empty = (torch.empty((nq, 0)), torch.empty((nq, 0), dtype=torch.int64))
             return empty if group_by is None else empty + (torch.empty((nq, 0), dtype=torch.int64),)
+        if keys is not None:
+            if group_by is not None:
+                raise ValueError("search_batch: keys= and group_by= do not combine")
+            return self._gpu.search_where(queries, k, self.key_values(keys), lo, hi,
+                                          allow=None if allow is None else self._allow(allow))
         if group_by is not None:
             groups = group_by if isinstance(group_by, GroupPlan) else self.group_ids(group_by)
             return self._gpu.search_grouped(queries, k, groups, allow=None if allow is None else self._allow(allow))

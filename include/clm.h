@@ -366,12 +366,43 @@ enum { CLM_MASK_EXACT = 1 << 30, CLM_MASK_PASS = 1 << 29, CLM_MASK_GATHER = 1 <<
 int clm_index_search_masked(clm_index* idx, const void* q, int q_dtype, int64_t nq, int k,
                             const uint32_t* allow, int flags, float* out_scores, int64_t* out_idx, void* stream);
 
+/* Keyed search: exact top-k under one key range PER QUERY, in one batched pass. keys [size] holds one
+ * int32 per index row in local row order (row j has global id offset + j), lo / hi [nq] one inclusive
+ * range per query: row j is open to query i iff lo[i] <= keys[j] <= hi[i]. Row i of the result is bit
+ * for bit row 0 of clm_index_search_masked(q_i, k, mask_i) with mask_i = the rows open to query i: the
+ * same order (NaN first, exact score descending, global id ascending), the same exact scores and global
+ * ids, (-inf, -1) past the number of open rows. An empty range (lo[i] > hi[i]) or one no key falls in
+ * gives a row of pads. A timestamp bound, a category (lo == hi) and a price band take this form once the
+ * values are mapped to their ranks; a key no range can hold (-1 below ranges that start at 0) closes a
+ * row to every query, which is how a batch-wide mask combines with the ranges.
+ * Two routes, the same bits on each. exact: windows of exact scores, the closed entries of each query set
+ * to -inf, the exact scan's top-k. pass: a strided sample of min(size, 2^18, round_up(max(8192, k * size
+ * / 256), 256)) rows, struck out per query, gives each query a threshold (-inf with fewer than k open
+ * sample rows), one fp16 MFMA pass lists the open rows that reach it, they are re-scored exactly; a
+ * query whose list overflowed 2,048 entries or ended short of min(k, n_in[i]) is redone by the exact
+ * route. The sample only sets the cost: its open rows are rows of the index, so the threshold never
+ * cuts below k of them. flags: 0 = the pass route unless the index holds a zero or non-finite row norm,
+ * $CLM_SEARCH_FULL=1, dim > 8192, k > 256 or size < 4 * round_up(max(8192, k * size / 256), 256);
+ * CLM_MASK_EXACT asks for the exact route, CLM_MASK_PASS for the pass route (taken with finite row
+ * norms, k <= 256, dim <= 8192). clm_index_stats2 entries 20 / 21 say which route served.
+ * n_in [nq] (or NULL): the number of rows in each query's range, which spares the exact redo of a query
+ * whose range holds fewer than k rows (with NULL every list short of k is redone). The pass route checks
+ * it from one side: a query that lists more rows than n_in[i] says its range holds is CLM_E_ARG.
+ * keys are copied into the index's workspace on every call; keys, lo, hi, n_in and the outputs may each be
+ * host or device pointers. q [nq, dim] CLM_F32|CLM_F16; 1 <= k <= 1024 (there is no gather route to serve
+ * a larger k). The call keeps no state. CLM_E_ARG: a null index, q, keys, lo, hi or output with nq > 0, a
+ * dtype other than f32 / f16, nq < 0, k outside [1, 1024], flags other than 0 / CLM_MASK_EXACT /
+ * CLM_MASK_PASS (CLM_MASK_GATHER among them), an empty index. nq == 0 is CLM_OK. */
+int clm_index_search_keyed(clm_index* idx, const void* q, int q_dtype, int64_t nq, int k, const int32_t* keys,
+                           const int32_t* lo, const int32_t* hi, const int64_t* n_in, int flags,
+                           float* out_scores, int64_t* out_idx, void* stream);
+
 /* search-path counters since creation: queries served by the sampled single-pass bounded
  * search (`filtered`), by the exact scan or the fp16-scan-bounded search (`exact`), and
  * bounded queries whose candidate list overflowed (redone by a whole-list pass, or by the exact
  * scan when the list is longer than 8192 / k chunks of 4096) */
 int clm_index_stats(const clm_index* idx, int64_t* filtered, int64_t* exact, int64_t* overflow);
-/* out[0..n), n <= 20: sampled bounded, fp16-scan bounded, full exact scan, overflow re-runs, then the
+/* out[0..n), n <= 22: sampled bounded, fp16-scan bounded, full exact scan, overflow re-runs, then the
  * sampled queries whose filter pass ran on the G2 256 x 192 tiles / on gemm_kernel 256 x 256 (chosen
  * per query block from the block's sampled candidate counts: near-duplicate blocks take the latter),
  * then the queries served by the small-batch streaming search (nq <= 16 on a large index: one pass
@@ -382,7 +413,8 @@ int clm_index_stats(const clm_index* idx, int64_t* filtered, int64_t* exact, int
  * its capacity, then the threshold-search queries served by the MFMA pass, by the exact route, and
  * those whose candidate list overflowed its capacity, then the clm_index_search_masked queries served
  * by the pass route, by the gather route and by the exact route (a pass-route query redone exactly
- * counts as exact) */
+ * counts as exact), then (entries 20 / 21) the clm_index_search_keyed queries served by the pass route
+ * and by the exact route (a redone query counts as exact) */
 int clm_index_stats2(const clm_index* idx, int64_t* out, int n);
 
 /* full cosine matrix, exact: out [nq, n] f32 = fp32(cos64(q_i, c_j)), any dim */
@@ -457,6 +489,18 @@ int clm_gemm_select(int hip_device, int epilogue, int config, const void* A, int
                     int cap, int64_t base, const uint32_t* cbound, uint32_t* above, float* lse_part,
                     int64_t lse_ld, float lse_c, const uint32_t* mask, int m_fastest, void* stream);
 int clm_value_bounds(int hip_device, const float* v, int64_t n, uint32_t* keys, void* stream);
+/* clm_gemm_select_keyed: clm_gemm_select for CLM_EPI_FILTER_KEYS (test hook; clm_gemm_select itself refuses
+ * that epilogue: it has no room for the arguments). CLM_EPI_FILTER with one open test per (row, column):
+ * column n is tested for row m only where klo[m] <= keys[n] <= khi[m]; keys [N] (16-byte aligned), klo /
+ * khi [M], device pointers. Row m's count and appended (s, id) set are bit for bit what
+ * CLM_EPI_FILTER_MASK gives it under the mask of its open columns. Configs 1 and 8-11, -1 = heuristic;
+ * cbound, m_fastest and the CLM_E_ARG cases as clm_gemm_select, plus null or misaligned keys, null klo / khi. */
+enum { CLM_EPI_FILTER_KEYS = 9 };
+int clm_gemm_select_keyed(int hip_device, int config, const void* A, int64_t lda, const void* W, int64_t ldw, int M,
+                          int N, int K, const float* rscale, const float* cscale, const float* theta,
+                          int64_t theta_ld, int* cnt, float* cand_s, int64_t* cand_i, int cap, int64_t base,
+                          const uint32_t* cbound, const int32_t* keys, const int32_t* klo, const int32_t* khi,
+                          int m_fastest, void* stream);
 /* diagnostic flags (micro-benchmarks and tests only; 0 in production), initialised from
  * $CLM_GEMM_DEBUG: for later clm_gemm / clm_gemm_select calls bit 0 = skip the epilogue (accumulators kept
  * live), bit 1 = run the epilogue but drop every store, bit 2 = one tile per workgroup
