@@ -39,10 +39,7 @@ int clm_index_destroy(clm_index* x) {
   if (!x) return CLM_OK;
   DeviceGuard g(x->dev);
   (void)hipDeviceSynchronize();
-  for (void* p : {(void*)x->rows, (void*)x->inv, (void*)x->rows32, x->ws, x->ws2, x->ws3, x->ws4, (void*)x->samp,
-                  (void*)x->samp_inv, (void*)x->inv_keys, x->mut, (void*)x->res_s, (void*)x->res_i, (void*)x->rg_comp,
-                  (void*)x->rg_comp2, x->rg_items})
-    if (p) (void)hipFree(p);
+  index_free_buffers(x);
   delete x;
   return CLM_OK;
 }
@@ -394,21 +391,15 @@ int clm_index_read(clm_index* x, int64_t start, int64_t n, float* dst, void* str
 
 int clm_index_stats(const clm_index* x, int64_t* filtered, int64_t* exact, int64_t* overflow) {
   if (!x) return fail(CLM_E_ARG, "null index");
-  if (filtered) *filtered = x->search_stats[0];
-  if (exact) *exact = x->search_stats[1] + x->search_stats[3];
-  if (overflow) *overflow = x->search_stats[2];
+  if (filtered) *filtered = x->search_stats[ST_BOUNDED_SAMPLED];
+  if (exact) *exact = x->search_stats[ST_EXACT_SCAN] + x->search_stats[ST_BOUNDED_SCAN];
+  if (overflow) *overflow = x->search_stats[ST_OVERFLOW];
   return CLM_OK;
 }
 
 int clm_index_stats2(const clm_index* x, int64_t* out, int n) {
   if (!x || !out || n < 0) return fail(CLM_E_ARG, "bad argument");
-  const int64_t v[22] = {x->search_stats[0], x->search_stats[3], x->search_stats[1], x->search_stats[2],
-                         x->search_stats[4], x->search_stats[5], x->search_stats[6], x->search_stats[7],
-                         x->search_stats[8], x->search_stats[9], x->search_stats[10], x->search_stats[11],
-                         x->search_stats[12], x->search_stats[13], x->search_stats[14], x->search_stats[15],
-                         x->search_stats[16], x->search_stats[17], x->search_stats[18], x->search_stats[19],
-                         x->search_stats[20], x->search_stats[21]};
-  for (int i = 0; i < n && i < 22; ++i) out[i] = v[i];
+  for (int i = 0; i < n && i < ST_COUNT; ++i) out[i] = x->search_stats[i];
   return CLM_OK;
 }
 

@@ -4,8 +4,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 #include <cstring>
+#include <initializer_list>
 #include <string>
 
 #include "clm.h"
@@ -71,10 +73,33 @@ struct Layout {
 }  // namespace capi
 }  // namespace clm
 
-// Every device buffer below is owned by the index and released by clm_index_destroy. The filtered
-// search's gather route (capi_search.cpp masked_gather) builds a temporary clm_index on the stack
-// around gathered rows, lends it ws2 / ws3 / ws4 and frees every other lazily allocated buffer when
-// it returns: a new device buffer added here must be added to both lists.
+// The route counters of an index (clm_index::search_stats), in the order clm_index_stats2 reports them.
+enum SearchStat {
+  // queries served by the sampled bounded search / the bounded search with the chunked fp16 scan as
+  // step 1 / the full exact scan / the overflow re-runs
+  ST_BOUNDED_SAMPLED, ST_BOUNDED_SCAN, ST_EXACT_SCAN, ST_OVERFLOW,
+  // queries whose filter pass ran on G2 256 x 192 / gemm_kernel 256 x 256 (dense blocks)
+  ST_TILE_G2, ST_TILE_DENSE,
+  ST_SMALL,   // queries served by the small-batch streaming search (search_small)
+  // rank queries served by the EPI_RANK band pass / by the exact route, those of the latter whose
+  // band list overflowed its capacity, band rows re-scored for the queries of ST_RANK_BAND
+  ST_RANK_BAND, ST_RANK_EXACT, ST_RANK_OVERFLOW, ST_RANK_BAND_ROWS,
+  // log-sum-exp queries served by the EPI_LSE pass / by the exact route, queries whose EPI_LSE band
+  // list overflowed its capacity
+  ST_LSE_FAST, ST_LSE_EXACT, ST_LSE_OVERFLOW,
+  // threshold-search queries served by the EPI_FILTER pass / by the exact route, those whose
+  // candidate list overflowed its capacity
+  ST_RANGE_FAST, ST_RANGE_EXACT, ST_RANGE_OVERFLOW,
+  // masked-search queries served by the pass route / the gather route / the exact route (a query of
+  // the other two redone exactly counts in ST_MASK_EXACT)
+  ST_MASK_PASS, ST_MASK_GATHER, ST_MASK_EXACT,
+  // keyed-search queries served by the pass route / the exact route (a redone query counts in the latter)
+  ST_KEY_PASS, ST_KEY_EXACT,
+  ST_COUNT
+};
+
+// Every device buffer below is owned by the index and released by index_free_buffers (after the
+// struct), the one list of them: a new device buffer is added there.
 struct clm_index {
   int dev = 0;
   int64_t cap = 0, n = 0, dim = 0, offset = 0;
@@ -98,21 +123,7 @@ struct clm_index {
   unsigned* inv_keys = nullptr; int64_t inv_keys_n = -1;
   // staging of clm_index_remove / clm_index_update: MUTATE_STAGE_BYTES, allocated by the first of them
   void* mut = nullptr;
-  // queries served by: [0] sampled bounded search, [1] the full exact scan, [2] overflow re-runs,
-  // [3] bounded search with the chunked fp16 scan as step 1
-  // [4] / [5]: queries whose filter pass ran on G2 256 x 192 / gemm_kernel 256 x 256 (dense blocks)
-  // [6]: queries served by the small-batch streaming search (search_small)
-  // [7] / [8]: rank queries served by the EPI_RANK band pass / by the exact route, [9]: those of [8]
-  // whose band list overflowed its capacity, [10]: band rows re-scored for the queries of [7]
-  // [11] / [12]: log-sum-exp queries served by the EPI_LSE pass / by the exact route, [13]: queries
-  // whose EPI_LSE band list overflowed its capacity
-  // [14] / [15]: threshold-search queries served by the EPI_FILTER pass / by the exact route, [16]:
-  // those whose candidate list overflowed its capacity
-  // [17] / [18] / [19]: masked-search queries served by the pass route / the gather route / the exact
-  // route (a pass-route query redone exactly counts in [19])
-  // [20] / [21]: keyed-search queries served by the pass route / the exact route (a redone query counts
-  // in [21])
-  int64_t search_stats[22] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  int64_t search_stats[ST_COUNT] = {};
   // The held result of the last threshold search (clm_index_search_above / _rows): res_n entries
   // (exact score, global id) in CSR order, read by clm_index_search_above_read until the next
   // threshold search, reset, mutation or destroy (res_valid). rg_comp / rg_comp2: the composites it
@@ -122,3 +133,12 @@ struct clm_index {
   uint64_t* rg_comp2 = nullptr; int64_t rg_comp2_cap = 0;
   void* rg_items = nullptr; size_t rg_items_bytes = 0;
 };
+
+// Frees every device buffer of the index but those in `keep`: on loan or the caller's (the filtered
+// search's gather route builds a temporary clm_index around gathered rows and lends it ws2 / ws3 / ws4)
+inline void index_free_buffers(clm_index* x, std::initializer_list<const void*> keep = {}) {
+  for (void* p : {(void*)x->rows, (void*)x->inv, (void*)x->rows32, x->ws, x->ws2, x->ws3, x->ws4, (void*)x->samp,
+                  (void*)x->samp_inv, (void*)x->inv_keys, x->mut, (void*)x->res_s, (void*)x->res_i, (void*)x->rg_comp,
+                  (void*)x->rg_comp2, x->rg_items})
+    if (p && std::find(keep.begin(), keep.end(), p) == keep.end()) (void)hipFree(p);
+}

@@ -1,6 +1,11 @@
-// libclm C-ABI, searching the resident index: clm_index_search and its routes, exact retrieval ranks
-// and the streaming log-sum-exp, after the plumbing they share (query staging, band query blocks,
-// the exact routes' row windows, redoing a subset of the queries exactly).
+// libclm C-ABI, searching the resident index: clm_index_search and its routes, the filtered, keyed
+// and threshold searches, exact retrieval ranks and the streaming log-sum-exp, after the plumbing
+// they share: query staging (QueryStage), band query blocks, the exact routes' row windows, redoing
+// a subset of the queries exactly (redo_subset), the overflowed lists' gathered groups (wide_groups);
+// further down one row filter (RowFilter), one candidate pass (PassBufs, row_thresholds,
+// sample_scores, candidate_pass), the top-k entry points' result staging
+// (ResultStage) and the exact / fast router (whole_call_exact). The clm_* entry points have C linkage
+// from their declarations in clm.h; the counters are named by SearchStat (capi_internal.hpp).
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -15,6 +20,10 @@ using namespace clm;
 using namespace clm::capi;
 
 namespace {
+
+// environment knobs: set to a non-zero number / the number, or `def` when unset
+bool env_flag(const char* name) { const char* e = getenv(name); return e && atoi(e) != 0; }
+int64_t env_int(const char* name, int64_t def) { const char* e = getenv(name); return e ? atoll(e) : def; }
 
 // the rows the exact re-scoring reads, from row r0 on: the caller's fp32 rows where the index keeps
 // them, else its fp16 rows (which then ARE the caller's rows)
@@ -81,12 +90,12 @@ int stage_queries_f16(const clm_index* x, const QueryStage& s, int64_t nq, hipSt
 // least. Then balanced: the same number of blocks, equal sizes (multiples of 64 rows while that
 // stays within the cap).
 int64_t band_query_block(int64_t nq, int64_t bytes_per_query, int64_t floor) {
-  static const int64_t ws_mb = getenv("CLM_SEARCH_WS_MB") ? atoll(getenv("CLM_SEARCH_WS_MB")) : 8192;
+  static const int64_t ws_mb = env_int("CLM_SEARCH_WS_MB", 8192);
   // query-block cap ($CLM_SEARCH_QB, A/B): a block's fp16 queries are re-read from L2 by every
   // index tile; with the filter GEMM on G2 tiles 2560 beats 4096 (10 k queries: 100.5 k vs 97.7 k
   // QPS, profiles/r04_v7_search_qb_ab.txt), and the blocks are balanced (a cap of 4096 gives
   // 10 k = 3392 + 3392 + 3216 instead of 4096 + 4096 + 1808)
-  static const int64_t qb_cap = getenv("CLM_SEARCH_QB") ? std::max<int64_t>(64, atoll(getenv("CLM_SEARCH_QB"))) : 2560;
+  static const int64_t qb_cap = std::max<int64_t>(64, env_int("CLM_SEARCH_QB", 2560));
   int64_t nqb = std::min<int64_t>(nq, qb_cap);
   if (bytes_per_query > 0) {
     size_t fr = 0, tot = 0;
@@ -161,9 +170,42 @@ int redo_subset(clm_index* x, const std::vector<int64_t>& list, std::initializer
   return CLM_OK;
 }
 
-}  // namespace
+// Overflowed candidate lists are rebuilt by one more pass with this capacity (headroom over the first
+// pass's count: a different tile shape may round a score differently)
+int64_t wide_capacity(int64_t count) { return count + count / 8 + 256; }
+// ... in groups of at most G queries: their lists (12 B per slot, `cap` slots each) within 1 GiB,
+// at most 4096. Per group the id list is uploaded (gx), the queries' rows of the `in` arrays are
+// gathered into x->ws4 behind it and body(w, gathered in..., gx, g0, ng) runs; carve(lay, G) takes
+// the body's own buffers from the same workspace (w + their offsets). body drains the stream before
+// it returns CLM_OK (the next group rewrites gx and the buffers); every exit path drains it.
+template <class Carve, class Body>
+int wide_groups(clm_index* x, const std::vector<int64_t>& list, int64_t cap, std::initializer_list<RowArray> in,
+                hipStream_t st, Carve carve, Body body) {
+  const int64_t n = (int64_t)list.size();
+  const int64_t G = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(n, 4096), ((int64_t)1 << 30) / (cap * 12)));
+  Layout lay;
+  const size_t p_x = lay.take((size_t)G * 8);
+  std::vector<size_t> offs;
+  for (const RowArray& a : in) offs.push_back(lay.take((size_t)G * a.row_bytes));
+  carve(lay, G);
+  if (int r = grow(&x->ws4, &x->ws4_bytes, lay.total())) return r;
+  uint8_t* w = (uint8_t*)x->ws4;
+  int64_t* gx = (int64_t*)(w + p_x);
+  std::vector<void*> g;
+  for (size_t o : offs) g.push_back(w + o);
+  auto group = [&](int64_t g0, int64_t ng) -> int {
+    HIPCHK(hipMemcpyAsync(gx, list.data() + g0, (size_t)ng * 8, hipMemcpyHostToDevice, st));
+    size_t j = 0;
+    for (const RowArray& a : in) KCHK(gather_rows(a.base, a.row_bytes, gx, ng, a.row_bytes, g[j++], a.row_bytes, false, st));
+    return body(w, g.data(), gx, g0, ng);
+  };
+  int r = CLM_OK;
+  for (int64_t g0 = 0; g0 < n && r == CLM_OK; g0 += G) r = group(g0, std::min(G, n - g0));
+  (void)hipStreamSynchronize(st);   // `list` (the source of gx) may go out of scope
+  return r;
+}
 
-extern "C" {
+}  // namespace
 
 // The MFMA pass scores fp16 unit-rounded operands: |fp16-pass score - exact cosine| <= 2.05e-3
 // (each side's rounding moves a cosine by <= 2u, u = 2^-11, plus fp32 accumulation of <= 1024
@@ -176,18 +218,32 @@ constexpr float RESCORE_MARGIN = 5e-3f;
 constexpr int MARGIN_MAX_DIM = 8192;
 constexpr int CAND_CAP = 2048;
 
-// Chunked scan: score chunks [nqb, ch] -- fp16 MFMA (EPI_SCORE GEMM) or exact fp64 cosines
-// (exact_scores) -- radix top-k per chunk row, merge of the chunk lists. Any k <= 1024, any N.
-// allow (exact scan only): the filter of a filtered search -- its prepared words -- or of a keyed one
-// -- the keys [N] and the ranges of these nq queries. Every window's disallowed entries become -inf
-// before its top-k (mask_fill / key_fill), so they sort behind every allowed row
-struct ScanFilter {
+// The rows a search may return: those of a filtered search's prepared mask words, or of a keyed
+// search's keys [N] and per-query ranges lo / hi [nq]; empty: every row (the unfiltered search).
+struct RowFilter {
   const uint32_t* words = nullptr;
   const int32_t *keys = nullptr, *lo = nullptr, *hi = nullptr;
+  // exact scores [nb, rn] of the queries from q0 against the rows from r0: disallowed entries -> -inf
+  hipError_t strike(float* sc, int64_t ld, int64_t q0, int64_t nb, int64_t r0, int64_t rn, hipStream_t st) const {
+    if (words) return mask_fill(sc, ld, nb, rn, r0, words, st);
+    if (keys) return key_fill(sc, ld, nb, rn, r0, keys, lo + q0, hi + q0, st);
+    return hipSuccess;
+  }
+  // the filter pass of the query block from q0: its operands set in g, its epilogue returned
+  int arm(GemmArgs& g, int64_t q0) const {
+    if (words) { g.mask = words; return EPI_FILTER_MASK; }
+    if (keys) { g.keys = keys; g.klo = lo + q0; g.khi = hi + q0; return EPI_FILTER_KEYS; }
+    return EPI_FILTER;
+  }
 };
+
+// Chunked scan: score chunks [nqb, ch] -- fp16 MFMA (EPI_SCORE GEMM) or exact fp64 cosines
+// (exact_scores) -- radix top-k per chunk row, merge of the chunk lists. Any k <= 1024, any N.
+// allow (exact scan only): the rows open to each query. Every window's disallowed entries become
+// -inf before its top-k (RowFilter::strike), so they sort behind every allowed row
 static int search_scan(clm_index* x, bool exact, const u16* q16, const float* qinv, const float* q32,
                        const double* qn, int64_t nq, int k, float* osc, int64_t* oix, hipStream_t st,
-                       const ScanFilter& allow = ScanFilter{}) {
+                       const RowFilter& allow = RowFilter{}) {
   const int dim = (int)x->dim;
   const int64_t N = x->n;
   const size_t budget = (size_t)512 << 20;
@@ -221,8 +277,7 @@ static int search_scan(clm_index* x, bool exact, const u16* q16, const float* qi
       if (exact) {
         const ExactRows er = exact_rows(x, r0);
         KCHK(exact_scores(q32 + q0 * dim, qn + q0, nb, er.p, er.f16, rn, dim, sc, ch, st));
-        if (allow.words) KCHK(mask_fill(sc, ch, nb, rn, r0, allow.words, st));
-        if (allow.keys) KCHK(key_fill(sc, ch, nb, rn, r0, allow.keys, allow.lo + q0, allow.hi + q0, st));
+        KCHK(allow.strike(sc, ch, q0, nb, r0, rn, st));
       } else {
         GemmArgs ga{};
         ga.A = q16 + q0 * dim; ga.lda = dim; ga.W = x->rows + r0 * dim; ga.ldw = dim;
@@ -292,7 +347,7 @@ static const unsigned* inv_keys_get(clm_index* x, hipStream_t st) {
 }
 // ... for the search's filter passes: null (no skip test) when $CLM_FILTER_SKIP=0 (A/B)
 static const unsigned* inv_keys_of(clm_index* x, hipStream_t st) {
-  static const bool on = !getenv("CLM_FILTER_SKIP") || atoi(getenv("CLM_FILTER_SKIP")) != 0;
+  static const bool on = env_int("CLM_FILTER_SKIP", 1) != 0;
   return on ? inv_keys_get(x, st) : nullptr;
 }
 
@@ -325,106 +380,86 @@ static int inv_norms_finite(clm_index* x, hipStream_t st, bool* ok, const unsign
   return CLM_OK;
 }
 
+// The tile config of a filter pass whose lists are long (overflowed, or estimated to): appends
+// dominate such a pass, where gemm_kernel's 256 x 256 FILTER epilogue beats G2's (near-duplicate leg
+// 73.7 k vs 66.0 k QPS, profiles/r04_v7_neardup_ab.txt); -1 (the heuristic's) under $CLM_GEMM_CFG
+static int dense_cfg() { static const int cfg = getenv("CLM_GEMM_CFG") ? -1 : 1; return cfg; }
+
 // Overflowed queries, wide path: their fp16 rows, inverse norms, fp32 rows, norms and filter
-// thresholds are gathered, the EPI_FILTER GEMM streams the index once more for just them with a
-// capacity of cap[j] (the first pass's count plus headroom), and rescore_wide + topk_merge pick the
-// exact top k from the whole list; results are scattered back to the queries' rows. Queries whose
-// list still exceeds its capacity are appended to `full` (the exact scan redoes them).
+// thresholds are gathered (wide_groups), the EPI_FILTER GEMM streams the index once more for just
+// them with a capacity of cap[j] (the first pass's count plus headroom), and rescore_wide + topk_merge
+// pick the exact top k from the whole list; results are scattered back to the queries' rows. Queries
+// whose list still exceeds its capacity are appended to `full` (the exact scan redoes them).
 static int overflow_wide(clm_index* x, const std::vector<int64_t>& qs, const std::vector<int64_t>& cap,
-                         const u16* q16, const float* qinv, const float* q32, const double* qn, const float* th,
-                         int k, float* osc, int64_t* oix, std::vector<int64_t>& full, hipStream_t st) {
+                         const QueryStage& q, const float* th, int k, float* osc, int64_t* oix,
+                         std::vector<int64_t>& full, hipStream_t st) {
   const int dim = (int)x->dim;
-  const int64_t n = (int64_t)qs.size();
   const ExactRows xr = exact_rows(x);
   int64_t cap_max = 0;
   for (int64_t c : cap) cap_max = std::max(cap_max, c);
   cap_max = round_up(cap_max, RESCORE_WIDE_CHUNK);
   const int64_t nch = cap_max / RESCORE_WIDE_CHUNK;
-  // queries per group: candidate lists (12 B per slot) within ~1 GB, at most 4096
-  const int64_t G = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(n, 4096), (int64_t)(1 << 30) / (cap_max * 12)));
-  Layout lay;
-  const size_t p_x = lay.take((size_t)G * 8), p_q16 = lay.take((size_t)G * dim * 2), p_qi = lay.take((size_t)G * 4),
-               p_q32 = lay.take((size_t)G * dim * 4), p_qn = lay.take((size_t)G * 8), p_th = lay.take((size_t)G * 4),
-               p_cnt = lay.take((size_t)G * 4), p_cs = lay.take((size_t)G * cap_max * 4), p_ci = lay.take((size_t)G * cap_max * 8),
-               p_ps = lay.take((size_t)G * nch * k * 4), p_pi = lay.take((size_t)G * nch * k * 8),
-               p_s = lay.take((size_t)G * k * 4), p_i = lay.take((size_t)G * k * 8);
-  if (int rg = grow(&x->ws4, &x->ws4_bytes, lay.total())) return rg;
-  uint8_t* w = (uint8_t*)x->ws4;
-  int64_t* gx = (int64_t*)(w + p_x);
-  int* cnt = (int*)(w + p_cnt);
-  std::vector<int> hcnt;
-  hipError_t e = hipSuccess;
-  for (int64_t g0 = 0; g0 < n && e == hipSuccess; g0 += G) {
-    const int64_t ng = std::min(G, n - g0);
-    e = hipMemcpyAsync(gx, qs.data() + g0, (size_t)ng * 8, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = gather_rows(q16, (int64_t)dim * 2, gx, ng, (int64_t)dim * 2, w + p_q16, (int64_t)dim * 2, false, st);
-    if (e == hipSuccess) e = gather_rows(qinv, 4, gx, ng, 4, w + p_qi, 4, false, st);
-    if (e == hipSuccess) e = gather_rows(q32, (int64_t)dim * 4, gx, ng, (int64_t)dim * 4, w + p_q32, (int64_t)dim * 4, false, st);
-    if (e == hipSuccess) e = gather_rows(qn, 8, gx, ng, 8, w + p_qn, 8, false, st);
-    if (e == hipSuccess) e = gather_rows(th, 4, gx, ng, 4, w + p_th, 4, false, st);
-    if (e == hipSuccess) e = hipMemsetAsync(cnt, 0, (size_t)ng * 4, st);
-    if (e != hipSuccess) break;
-    GemmArgs gf = index_pass(x, (const u16*)(w + p_q16), (const float*)(w + p_qi), ng, (const float*)(w + p_th), cnt,
-                             (int64_t*)(w + p_ci), cap_max);
-    gf.cand_s = (float*)(w + p_cs);
-    gf.cbound = inv_keys_of(x, st);
-    // these queries' lists overflowed: appends dominate this pass, where gemm_kernel's 256 x 256
-    // FILTER epilogue beats G2's (near-duplicate leg 73.7 k vs 66.0 k QPS,
-    // profiles/r04_v7_neardup_ab.txt)
-    static const int ocfg = getenv("CLM_GEMM_CFG") ? -1 : 1;
-    if ((e = gemm_cfg(false, EPI_FILTER, ocfg, gf, st)) != hipSuccess) break;
-    if ((e = rescore_wide((const int64_t*)(w + p_ci), cnt, cap_max, (const float*)(w + p_q32),
-                          (const double*)(w + p_qn), dim, xr.p, xr.f16, x->offset, ng, k, (float*)(w + p_ps),
-                          (int64_t*)(w + p_pi), st)) != hipSuccess) break;
-    if ((e = topk_merge((const float*)(w + p_ps), (const int64_t*)(w + p_pi), ng, (int)nch, k, k, (float*)(w + p_s),
-                        (int64_t*)(w + p_i), st)) != hipSuccess) break;
-    hcnt.resize(ng);
-    if ((e = hipMemcpyAsync(hcnt.data(), cnt, (size_t)ng * 4, hipMemcpyDeviceToHost, st)) != hipSuccess) break;
-    if ((e = hipStreamSynchronize(st)) != hipSuccess) break;
-    // scatter the complete lists' results; a list past its capacity goes to the exact scan
-    std::vector<int64_t> done;
-    std::vector<int64_t> rows_ok;
-    for (int64_t j = 0; j < ng; ++j) {
-      if (hcnt[j] > cap_max) full.push_back(qs[g0 + j]);
-      else { done.push_back(qs[g0 + j]); rows_ok.push_back(j); }
-    }
-    if (done.size() == (size_t)ng) {
-      e = gather_rows(w + p_s, (int64_t)k * 4, gx, ng, (int64_t)k * 4, osc, (int64_t)k * 4, true, st);
-      if (e == hipSuccess) e = gather_rows(w + p_i, (int64_t)k * 8, gx, ng, (int64_t)k * 8, oix, (int64_t)k * 8, true, st);
-    } else {
-      for (size_t j = 0; j < done.size() && e == hipSuccess; ++j) {
-        e = hipMemcpyAsync(osc + done[j] * k, (float*)(w + p_s) + rows_ok[j] * k, (size_t)k * 4,
-                           hipMemcpyDeviceToDevice, st);
-        if (e == hipSuccess)
-          e = hipMemcpyAsync(oix + done[j] * k, (int64_t*)(w + p_i) + rows_ok[j] * k, (size_t)k * 8,
-                             hipMemcpyDeviceToDevice, st);
-      }
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(st);   // gx is rewritten by the next group
-  }
-  (void)hipStreamSynchronize(st);
-  if (e != hipSuccess) return fail(CLM_E_HIP, std::string("overflow (wide): ") + hipGetErrorString(e));
-  return CLM_OK;
+  size_t p_cnt, p_cs, p_ci, p_ps, p_pi, p_s, p_i;
+  return wide_groups(   // gathered: in[0] = q16, [1] = qinv, [2] = q32, [3] = qn, [4] = th
+      x, qs, cap_max, {{q.q16, (int64_t)dim * 2}, {q.qinv, 4}, {q.q32, (int64_t)dim * 4}, {q.qn, 8}, {th, 4}}, st,
+      [&](Layout& lay, int64_t G) {
+        p_cnt = lay.take((size_t)G * 4); p_cs = lay.take((size_t)G * cap_max * 4); p_ci = lay.take((size_t)G * cap_max * 8);
+        p_ps = lay.take((size_t)G * nch * k * 4); p_pi = lay.take((size_t)G * nch * k * 8);
+        p_s = lay.take((size_t)G * k * 4); p_i = lay.take((size_t)G * k * 8);
+      },
+      [&](uint8_t* w, void* const* in, const int64_t* gx, int64_t g0, int64_t ng) -> int {
+        int* cnt = (int*)(w + p_cnt);
+        float* gs = (float*)(w + p_s);
+        int64_t* gi = (int64_t*)(w + p_i);
+        HIPCHK(hipMemsetAsync(cnt, 0, (size_t)ng * 4, st));
+        GemmArgs gf = index_pass(x, (const u16*)in[0], (const float*)in[1], ng, (const float*)in[4], cnt,
+                                 (int64_t*)(w + p_ci), cap_max);
+        gf.cand_s = (float*)(w + p_cs);
+        gf.cbound = inv_keys_of(x, st);
+        KCHK(gemm_cfg(false, EPI_FILTER, dense_cfg(), gf, st));
+        KCHK(rescore_wide((const int64_t*)(w + p_ci), cnt, cap_max, (const float*)in[2], (const double*)in[3], dim, xr.p,
+                          xr.f16, x->offset, ng, k, (float*)(w + p_ps), (int64_t*)(w + p_pi), st));
+        KCHK(topk_merge((const float*)(w + p_ps), (const int64_t*)(w + p_pi), ng, (int)nch, k, k, gs, gi, st));
+        std::vector<int> hcnt(ng);
+        HIPCHK(hipMemcpyAsync(hcnt.data(), cnt, (size_t)ng * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        // scatter the complete lists' results; a list past its capacity goes to the exact scan
+        std::vector<int64_t> rows_ok;
+        for (int64_t j = 0; j < ng; ++j) {
+          if (hcnt[j] > cap_max) full.push_back(qs[g0 + j]);
+          else rows_ok.push_back(j);
+        }
+        if (rows_ok.size() == (size_t)ng) {
+          KCHK(gather_rows(gs, (int64_t)k * 4, gx, ng, (int64_t)k * 4, osc, (int64_t)k * 4, true, st));
+          KCHK(gather_rows(gi, (int64_t)k * 8, gx, ng, (int64_t)k * 8, oix, (int64_t)k * 8, true, st));
+        } else {
+          for (int64_t j : rows_ok) {
+            const int64_t dst = qs[g0 + j];
+            HIPCHK(hipMemcpyAsync(osc + dst * k, gs + j * k, (size_t)k * 4, hipMemcpyDeviceToDevice, st));
+            HIPCHK(hipMemcpyAsync(oix + dst * k, gi + j * k, (size_t)k * 8, hipMemcpyDeviceToDevice, st));
+          }
+        }
+        HIPCHK(hipStreamSynchronize(st));   // gx is rewritten by the next group
+        return CLM_OK;
+      });
 }
 
 // Candidate lists that overflowed CAND_CAP (queries `overflow`, first-pass counts `ocount`): rebuilt
 // whole by a second filter pass (overflow_wide) or redone by the exact scan (search_bounded,
 // search_small). th: every query's filter threshold. `exact`: further queries for that one exact scan.
 static int finish_overflow(clm_index* x, const std::vector<int64_t>& overflow, const std::vector<int64_t>& ocount,
-                           const u16* q16, const float* qinv, const float* q32, const double* qn, const float* th,
-                           int k, float* osc, int64_t* oix, hipStream_t st,
+                           const QueryStage& qs, const float* th, int k, float* osc, int64_t* oix, hipStream_t st,
                            const std::vector<int64_t>* exact = nullptr) {
   int r;
   // Candidate lists beyond CAND_CAP (near-duplicate rows inside the window). Lists of up to
   // (SORT_MAX / k) chunks are rebuilt whole by a second filter pass over just those queries and
   // re-scored chunk-wise (overflow_wide); longer ones are redone by the exact scan, all of them in
   // ONE scan (the index is streamed once per query block of search_scan, not once per query).
-  x->search_stats[2] += (int64_t)overflow.size();
+  x->search_stats[ST_OVERFLOW] += (int64_t)overflow.size();
   std::vector<int64_t> wide, wcount, full;
   if (exact) full = *exact;
   for (size_t j = 0; j < overflow.size(); ++j) {
-    // headroom over the first pass's count: a different tile shape may round a score differently
-    const int64_t cap2 = ocount[j] + ocount[j] / 8 + 256;
+    const int64_t cap2 = wide_capacity(ocount[j]);
     if ((cap2 + RESCORE_WIDE_CHUNK - 1) / RESCORE_WIDE_CHUNK * k <= 8192) {
       wide.push_back(overflow[j]);
       wcount.push_back(cap2);
@@ -432,15 +467,101 @@ static int finish_overflow(clm_index* x, const std::vector<int64_t>& overflow, c
       full.push_back(overflow[j]);
     }
   }
-  if (!wide.empty() && (r = overflow_wide(x, wide, wcount, q16, qinv, q32, qn, th, k, osc, oix, full, st))) return r;
+  if (!wide.empty() && (r = overflow_wide(x, wide, wcount, qs, th, k, osc, oix, full, st))) return r;
   // the rest redone by the exact scan, all of them in ONE scan; their rows of osc / oix are replaced
   // (x->ws4: overflow_wide is done with it, it drains its stream)
-  return redo_subset(x, full, {{q32, x->dim * 4}, {qn, 8}}, {{osc, (int64_t)k * 4}, {oix, (int64_t)k * 8}}, "overflow", st,
-                     [&](void* const* in, void* const* out) -> int {
+  return redo_subset(x, full, {{qs.q32, x->dim * 4}, {qs.qn, 8}}, {{osc, (int64_t)k * 4}, {oix, (int64_t)k * 8}}, "overflow",
+                     st, [&](void* const* in, void* const* out) -> int {
                        return search_scan(x, true, nullptr, nullptr, (const float*)in[0], (const double*)in[1],
                                           (int64_t)full.size(), k, (float*)out[0], (int64_t*)out[1], st);
                      });
 }
+
+// ---- what the candidate passes share (search_bounded, search_small, masked_pass, keyed_pass) ----
+// $CLM_KTH_RADIX=1: the sampled thresholds through topk_rows (A/B, tests)
+static const bool g_kth_radix = env_flag("CLM_KTH_RADIX");
+// k-th values by one streaming pass (kth_thresholds and its fp16 variants)
+static bool kth_one_pass(int k) { return k <= 8 && !g_kth_radix; }
+
+// The buffers of a candidate pass over nq queries in blocks of nqb: a block's top-k scratch (ts / ti)
+// and candidate lists (cs / ci, CAND_CAP slots per query), every query's threshold (the overflow pass
+// reuses them) and count (read once, after the last block). take() from the Layout, bind() once grown.
+struct PassBufs {
+  size_t o_ts, o_ti, o_th, o_cnt, o_cs, o_ci;
+  float* ts; int64_t* ti; float* th; int* cnt; float* cs; int64_t* ci;
+  void take(Layout& lay, int64_t nq, int64_t nqb, int k) {
+    o_ts = lay.take((size_t)nqb * k * 4); o_ti = lay.take((size_t)nqb * k * 8);
+    o_th = lay.take((size_t)nq * 4); o_cnt = lay.take((size_t)nq * 4);
+    o_cs = lay.take((size_t)nqb * CAND_CAP * 4); o_ci = lay.take((size_t)nqb * CAND_CAP * 8);
+  }
+  void bind(void* ws) {
+    uint8_t* w = (uint8_t*)ws;
+    ts = (float*)(w + o_ts); ti = (int64_t*)(w + o_ti); th = (float*)(w + o_th); cnt = (int*)(w + o_cnt);
+    cs = (float*)(w + o_cs); ci = (int64_t*)(w + o_ci);
+  }
+};
+
+// th[q] = (k-th largest of row q of the scores [nb, C], row stride ld) - RESCORE_MARGIN: one
+// streaming pass (one_pass, where kth_one_pass(k)), else topk_rows into b's scratch + filter_thresholds
+static int row_thresholds(const float* sc, int64_t ld, int64_t nb, int64_t C, int k, bool one_pass, const PassBufs& b,
+                          float* th, hipStream_t st) {
+  if (one_pass) {
+    KCHK(kth_thresholds(sc, ld, nb, C, k, RESCORE_MARGIN, th, st));
+  } else {
+    KCHK(topk_rows(sc, ld, nb, C, k, 0, b.ts, b.ti, k, st));
+    KCHK(filter_thresholds(b.ts, k, nb, k, RESCORE_MARGIN, th, st));
+  }
+  return CLM_OK;
+}
+
+// The threshold sample's size: the k-th best of S rows sampled from `rows` ranks ~k * rows / S = div
+// among them, so ~div candidates per query; 8192 rows at least, a multiple of 256
+static int64_t sample_size(int k, int64_t rows, int64_t div = 256) {
+  return round_up(std::max<int64_t>(8192, (int64_t)k * rows / div), 256);
+}
+// whether the masked / keyed pass route can serve the call (fin: inv_norms_finite)
+static bool filter_pass_ok(const clm_index* x, bool fin, int k) {
+  return fin && k <= 256 && x->dim <= MARGIN_MAX_DIM && x->n <= 0x7FFFFFFF;
+}
+
+// fp16-pass scores [nb, S] (row stride ld) of the nb queries from q0 against S sample rows s16 with
+// inverse norms sinv. out16: 0 fp32 scores, 1 fp16, 2 fp16 maxima of groups of 4 rows (config 1,
+// 256 x 256: the group layout's tile)
+static hipError_t sample_scores(const QueryStage& qs, int64_t q0, int64_t nb, int dim, const u16* s16, const float* sinv,
+                                int64_t S, void* sc, int64_t ld, int out16, hipStream_t st) {
+  GemmArgs ga{};
+  ga.A = qs.q16 + q0 * dim; ga.lda = dim; ga.W = s16; ga.ldw = dim;
+  ga.M = (int)nb; ga.N = (int)S; ga.K = dim; ga.out = sc; ga.ldo = ld; ga.out16 = out16;
+  ga.rscale = qs.qinv + q0; ga.cscale = sinv;
+  return gemm_cfg(false, EPI_SCORE, out16 == 2 ? 1 : -1, ga, st);
+}
+
+// The candidate pass over the staged queries, block by block behind one memset of the counts: the
+// filter GEMM (index_pass against b.th, the filter's epilogue and operands, the tile config that
+// cfg(q0, nb, args) returns) lists the block's candidates, rescore_select writes its exact top k.
+// Then every count comes to the host (hcnt; drains the stream): what is overflowed or short is the caller's rule.
+template <class Cfg>
+static int candidate_pass(clm_index* x, const QueryStage& qs, int64_t nq, int64_t nqb, int k, const RowFilter& allow,
+                          const PassBufs& b, float* osc, int64_t* oix, std::vector<int>& hcnt, hipStream_t st, Cfg cfg) {
+  const int dim = (int)x->dim;
+  const ExactRows xr = exact_rows(x);
+  HIPCHK(hipMemsetAsync(b.cnt, 0, (size_t)nq * 4, st));
+  for (int64_t q0 = 0; q0 < nq; q0 += nqb) {
+    const int64_t nb = std::min(nqb, nq - q0);
+    GemmArgs gf = index_pass(x, qs.q16 + q0 * dim, qs.qinv + q0, nb, b.th + q0, b.cnt + q0, b.ci, CAND_CAP);
+    gf.cand_s = b.cs;
+    gf.cbound = inv_keys_of(x, st);
+    const int epi = allow.arm(gf, q0), config = cfg(q0, nb, gf);
+    KCHK(gemm_cfg(false, epi, config, gf, st));
+    KCHK(rescore_select(b.cs, b.ci, b.cnt + q0, CAND_CAP, qs.q32 + q0 * dim, qs.qn + q0, dim, xr.p, xr.f16, x->offset,
+                        RESCORE_MARGIN, nb, k, osc + q0 * k, oix + q0 * k, st));
+  }
+  hcnt.resize(nq);
+  HIPCHK(hipMemcpyAsync(hcnt.data(), b.cnt, (size_t)nq * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipStreamSynchronize(st));
+  return CLM_OK;
+}
+static int heuristic_cfg(int64_t, int64_t, GemmArgs&) { return -1; }
 
 // Bounded search (large N), per block of queries:
 //  1. theta[q] <= the fp16-pass k-th best score of q:
@@ -454,12 +575,8 @@ static int finish_overflow(clm_index* x, const std::vector<int64_t>& overflow, c
 //  3. rescore_select: candidates within the margin of their k-th are re-scored exactly against
 //     the caller's rows, sorted (score desc, index asc), top k written.
 //  Lists that overflowed CAND_CAP are redone by the full exact scan.
-// $CLM_KTH_RADIX=1: the sampled thresholds through topk_rows (A/B, tests)
-static const bool g_kth_radix = getenv("CLM_KTH_RADIX") && atoi(getenv("CLM_KTH_RADIX")) != 0;
-
-static int search_bounded(clm_index* x, bool sampled, int64_t S, const u16* q16, const float* qinv,
-                          const float* q32, const double* qn, int64_t nq, int k, float* osc, int64_t* oix,
-                          hipStream_t st) {
+static int search_bounded(clm_index* x, bool sampled, int64_t S, const QueryStage& qs, int64_t nq, int k, float* osc,
+                          int64_t* oix, hipStream_t st) {
   const int dim = (int)x->dim;
   const int64_t N = x->n;
   int r;
@@ -481,7 +598,7 @@ static int search_bounded(clm_index* x, bool sampled, int64_t S, const u16* q16,
   // the sample-score rows' stride: S (a multiple of 256 floats, 1 KB) plus 256 B, so the score
   // GEMM's 16-row column stores do not land every row at the same power-of-two address offset
   // ($CLM_SAMPLE_PAD floats, A/B)
-  static const int64_t spad = getenv("CLM_SAMPLE_PAD") ? atoll(getenv("CLM_SAMPLE_PAD")) : 64;
+  static const int64_t spad = env_int("CLM_SAMPLE_PAD", 64);
   const int64_t ldS = S + spad;
   // the sampled path's block is bounded by its sample-score matrix (nqb x S fp32), 256 queries at least
   const int64_t nqb = band_query_block(nq, sampled ? ldS * 4 : 0, 256);
@@ -489,110 +606,79 @@ static int search_bounded(clm_index* x, bool sampled, int64_t S, const u16* q16,
   // fp16 sample scores (rounded toward -inf: the k-th largest over them is <= the fp32 one, so
   // the thresholds only widen) where the one-pass k-th value path runs: half the bytes of the
   // phase's three passes ($CLM_SAMPLE_F32=1: fp32, A/B)
-  static const bool s32_env = getenv("CLM_SAMPLE_F32") && atoi(getenv("CLM_SAMPLE_F32")) != 0;
-  const bool s16 = sampled && k <= 8 && !g_kth_radix && !s32_env;
+  static const bool s32_env = env_flag("CLM_SAMPLE_F32");
+  const bool s16 = sampled && kth_one_pass(k) && !s32_env;
   // ... and stored as the maxima of groups of 4 sample rows (a subset of the scores: its k-th
   // largest is at most theirs, so θ stays a lower bound; 4x fewer bytes again). The dense-tile
   // estimate then counts groups, times 4 (an upper bound of the scores >= θ).
   // ($CLM_SAMPLE_GROUP=0: every score, A/B)
-  static const bool grp_env = !(getenv("CLM_SAMPLE_GROUP") && atoi(getenv("CLM_SAMPLE_GROUP")) == 0);
+  static const bool grp_env = env_int("CLM_SAMPLE_GROUP", 1) != 0;
   const bool sgrp = s16 && grp_env && S % 256 == 0;
   const int64_t Sc = sgrp ? S / 4 : S;             // stored values per sample-score row
   const int64_t ldC = sgrp ? S / 4 + 64 : ldS;     // their row stride
   const size_t o_sc = sampled ? lay.take((size_t)nqb * ldC * (s16 ? 2 : 4)) : 0;
-  const size_t o_ts = lay.take((size_t)nqb * k * 4);
-  const size_t o_ti = lay.take((size_t)nqb * k * 8);
-  const size_t o_th = lay.take((size_t)nq * 4);   // every query's threshold (the overflow pass reuses them)
-  const size_t o_cnt = lay.take((size_t)nq * 4);   // every query's candidate count (read once, after the last block)
   const size_t o_est = lay.take((size_t)nq * 4);
-  const size_t o_cs = lay.take((size_t)nqb * CAND_CAP * 4);
-  const size_t o_ci = lay.take((size_t)nqb * CAND_CAP * 8);
+  PassBufs b;
+  b.take(lay, nq, nqb, k);
   if ((r = grow(&x->ws2, &x->ws2_bytes, lay.total()))) return r;
-  uint8_t* w = (uint8_t*)x->ws2;
-  float* sc = (float*)(w + o_sc);
-  float* ts = (float*)(w + o_ts);
-  int64_t* ti = (int64_t*)(w + o_ti);
-  float* th = (float*)(w + o_th);
-  int* cnt = (int*)(w + o_cnt);
-  int* est = (int*)(w + o_est);
-  std::vector<int> hest;
-  float* cs = (float*)(w + o_cs);
-  int64_t* ci = (int64_t*)(w + o_ci);
-  const ExactRows xr = exact_rows(x);
-  std::vector<int> hcnt;
-  std::vector<int64_t> overflow, ocount;
+  b.bind(x->ws2);
+  float* sc = (float*)((uint8_t*)x->ws2 + o_sc);
+  int* est = (int*)((uint8_t*)x->ws2 + o_est);
+  float* th = b.th;
   // Phase 1, every block: the per-query thresholds (and, sampled, the estimated candidate counts)
   // -- no host round trip between blocks
   for (int64_t q0 = 0; q0 < nq; q0 += nqb) {
     const int64_t nb = std::min(nqb, nq - q0);
     if (sampled) {
-      GemmArgs ga{};
-      ga.A = q16 + q0 * dim; ga.lda = dim; ga.W = x->samp; ga.ldw = dim;
-      ga.M = (int)nb; ga.N = (int)S; ga.K = dim; ga.out = sc; ga.ldo = ldC; ga.out16 = sgrp ? 2 : s16 ? 1 : 0;
-      ga.rscale = qinv + q0; ga.cscale = x->samp_inv;
-      if (sgrp) KCHK(gemm_cfg(false, EPI_SCORE, 1, ga, st));   // config 1 (256 x 256): the group layout's tile
-      else KCHK(gemm(false, EPI_SCORE, ga, st));
+      KCHK(sample_scores(qs, q0, nb, dim, x->samp, x->samp_inv, S, sc, ldC, sgrp ? 2 : s16 ? 1 : 0, st));
       if (s16) {
         KCHK(kth_thresholds16((const u16*)sc, ldC, nb, Sc, k, RESCORE_MARGIN, th + q0, st));
         KCHK(count_ge16((const u16*)sc, ldC, nb, Sc, th + q0, est + q0, st));
       } else {
-        if (k <= 8 && !g_kth_radix) {   // one streaming pass for the k-th value alone
-          KCHK(kth_thresholds(sc, ldS, nb, S, k, RESCORE_MARGIN, th + q0, st));
-        } else {
-          KCHK(topk_rows(sc, ldS, nb, S, k, 0, ts, ti, k, st));
-          KCHK(filter_thresholds(ts, k, nb, k, RESCORE_MARGIN, th + q0, st));
-        }
+        if ((r = row_thresholds(sc, ldS, nb, S, k, kth_one_pass(k), b, th + q0, st))) return r;
         KCHK(count_ge(sc, ldS, nb, S, th + q0, est + q0, st));
       }
     } else {
-      if ((r = search_scan(x, false, q16 + q0 * dim, qinv + q0, nullptr, nullptr, nb, k, ts, ti, st))) return r;
-      KCHK(filter_thresholds(ts, k, nb, k, RESCORE_MARGIN, th + q0, st));
+      if ((r = search_scan(x, false, qs.q16 + q0 * dim, qs.qinv + q0, nullptr, nullptr, nb, k, b.ts, b.ti, st))) return r;
+      KCHK(filter_thresholds(b.ts, k, nb, k, RESCORE_MARGIN, th + q0, st));
     }
   }
   // Filter tile per block, from the block's own data: when most of its queries' candidate windows
   // hold more than CAND_CAP rows (near-duplicate rows: the sampled count above the threshold,
   // scaled by N / S), the appends dominate the pass and gemm_kernel's 256 x 256 FILTER epilogue is
-  // the faster one; otherwise G2's 256 x 192 (same candidates either way)
+  // the faster one (dense_cfg); otherwise G2's 256 x 192 (same candidates either way)
+  std::vector<int> hest, hcnt;
   if (sampled) {
     hest.resize(nq);
     HIPCHK(hipMemcpyAsync(hest.data(), est, (size_t)nq * 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
   }
-  HIPCHK(hipMemsetAsync(cnt, 0, (size_t)nq * 4, st));
+  // never clm_debug_set / $CLM_GEMM_DEBUG (those drop epilogues: the candidate lists would be
+  // empty and the top-k wrong); the filter pass's own timing knob is $CLM_SEARCH_EPI_DEBUG,
+  // read by tools only, whose results are discarded
+  static const int search_dbg = (int)env_int("CLM_SEARCH_EPI_DEBUG", 0) & 3;
   // Phase 2, every block: the filter pass and the exact re-score of its candidates
-  for (int64_t q0 = 0; q0 < nq; q0 += nqb) {
-    const int64_t nb = std::min(nqb, nq - q0);
+  r = candidate_pass(x, qs, nq, nqb, k, RowFilter{}, b, osc, oix, hcnt, st, [&](int64_t q0, int64_t nb, GemmArgs& gf) {
     bool dense = false;
     if (sampled) {
       int64_t over = 0;
       for (int64_t i = 0; i < nb; ++i) over += (double)hest[q0 + i] * (sgrp ? 4.0 : 1.0) * ((double)N / (double)S) > CAND_CAP;
       dense = 2 * over > nb;
     }
-    GemmArgs gf = index_pass(x, q16 + q0 * dim, qinv + q0, nb, th + q0, cnt + q0, ci, CAND_CAP);
-    gf.cand_s = cs;
-    gf.cbound = inv_keys_of(x, st);
-    // never clm_debug_set / $CLM_GEMM_DEBUG (those drop epilogues: the candidate lists would be
-    // empty and the top-k wrong); the filter pass's own timing knob is $CLM_SEARCH_EPI_DEBUG,
-    // read by tools only, whose results are discarded
-    static const int search_dbg = getenv("CLM_SEARCH_EPI_DEBUG") ? (atoi(getenv("CLM_SEARCH_EPI_DEBUG")) & 3) : 0;
     gf.debug = search_dbg;
-    static const bool cfg_forced = getenv("CLM_GEMM_CFG") != nullptr;
-    KCHK(gemm_cfg(false, EPI_FILTER, dense && !cfg_forced ? 1 : -1, gf, st));
-    x->search_stats[dense ? 5 : 4] += nb;
-    KCHK(rescore_select(cs, ci, cnt + q0, CAND_CAP, q32 + q0 * dim, qn + q0, dim, xr.p, xr.f16, x->offset,
-                        RESCORE_MARGIN, nb, k, osc + q0 * k, oix + q0 * k, st));
-  }
-  hcnt.resize(nq);
-  HIPCHK(hipMemcpyAsync(hcnt.data(), cnt, (size_t)nq * 4, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
+    x->search_stats[dense ? ST_TILE_DENSE : ST_TILE_G2] += nb;
+    return dense ? dense_cfg() : -1;
+  });
+  if (r) return r;
+  std::vector<int64_t> overflow, ocount;
   for (int64_t i = 0; i < nq; ++i)
     if (hcnt[i] > CAND_CAP) {
       overflow.push_back(i);
       ocount.push_back(hcnt[i]);
     }
-  x->search_stats[sampled ? 0 : 3] += nq - (int64_t)overflow.size();
+  x->search_stats[sampled ? ST_BOUNDED_SAMPLED : ST_BOUNDED_SCAN] += nq - (int64_t)overflow.size();
   if (overflow.empty()) return CLM_OK;
-  return finish_overflow(x, overflow, ocount, q16, qinv, q32, qn, th, k, osc, oix, st);
+  return finish_overflow(x, overflow, ocount, qs, th, k, osc, oix, st);
 }
 
 // Small query batches (nq <= 16) on a large index -- the reference's own pattern, one query per
@@ -618,8 +704,8 @@ static bool search_small_fits(const clm_index* x, int64_t nq, int k) {
          (nq - 1) * nchunk * 4 + 4 <= 0x7FFFFFF0LL;
 }
 
-static int search_small(clm_index* x, const u16* q16, const float* qinv, const float* q32, const double* qn,
-                        int64_t nq, int k, float* osc, int64_t* oix, hipStream_t st) {
+static int search_small(clm_index* x, const QueryStage& qs, int64_t nq, int k, float* osc, int64_t* oix,
+                        hipStream_t st) {
   const int dim = (int)x->dim;
   const int64_t N = x->n;
   const int64_t nchunk = (N + 255) / 256;
@@ -628,43 +714,36 @@ static int search_small(clm_index* x, const u16* q16, const float* qinv, const f
   Layout lay;
   const size_t o_sc = lay.take((size_t)N * ldq * 4);
   const size_t o_cm = lay.take((size_t)nq * nchunk * 4);
-  const size_t o_th = lay.take((size_t)nq * 4);
-  const size_t o_cnt = lay.take((size_t)nq * 4);
-  const size_t o_ts = lay.take((size_t)nq * k * 4);
-  const size_t o_ti = lay.take((size_t)nq * k * 8);
-  const size_t o_cs = lay.take((size_t)nq * CAND_CAP * 4);
-  const size_t o_ci = lay.take((size_t)nq * CAND_CAP * 8);
+  PassBufs b;   // one block of all nq queries
+  b.take(lay, nq, nq, k);
   const int64_t W = scan16_waves(nchunk, dim);   // k <= 8: every wave's 8 largest chunk maxima
   const int64_t ldw = W * 8;
   const size_t o_wt = lay.take((size_t)nq * ldw * 4);
   int r = grow(&x->ws2, &x->ws2_bytes, lay.total());
   if (r) return r;
   uint8_t* w = (uint8_t*)x->ws2;
+  b.bind(w);
   float* sc = (float*)(w + o_sc);
   float* cm = (float*)(w + o_cm);
-  float* th = (float*)(w + o_th);
-  int* cnt = (int*)(w + o_cnt);
+  float* wt = (float*)(w + o_wt);
   Scan16Args a{};
   a.rows = x->rows; a.inv = x->inv; a.N = N; a.dim = dim;
-  a.q16 = q16; a.qinv = qinv; a.nq = (int)nq;
+  a.q16 = qs.q16; a.qinv = qs.qinv; a.nq = (int)nq;
   a.out = sc; a.ldo = ldq; a.cmax = cm; a.nchunk = nchunk;
-  const bool wave_top = k <= 8 && !g_kth_radix && W * 8 >= k;
-  a.wtop = wave_top ? (float*)(w + o_wt) : nullptr; a.ldw = ldw;
+  const bool wave_top = kth_one_pass(k) && W * 8 >= k;
+  a.wtop = wave_top ? wt : nullptr; a.ldw = ldw;
   KCHK(scan16(a, st));
-  if (wave_top) {   // the k-th largest of the waves' top-8 lists = the k-th largest chunk maximum
-    KCHK(kth_thresholds((const float*)(w + o_wt), ldw, nq, ldw, k, RESCORE_MARGIN, th, st));
-  } else {
-    KCHK(topk_rows(cm, nchunk, nq, nchunk, k, 0, (float*)(w + o_ts), (int64_t*)(w + o_ti), k, st));
-    KCHK(filter_thresholds((const float*)(w + o_ts), k, nq, k, RESCORE_MARGIN, th, st));
-  }
-  HIPCHK(hipMemsetAsync(cnt, 0, (size_t)nq * 4, st));
-  KCHK(collect_ge(sc, (int)ldq, (int)nq, N, th, cnt, CAND_CAP, (float*)(w + o_cs), (int64_t*)(w + o_ci), x->offset,
-                  st));
+  // the k-th largest of the waves' top-8 lists = the k-th largest chunk maximum
+  if ((r = wave_top ? row_thresholds(wt, ldw, nq, ldw, k, true, b, b.th, st)
+                    : row_thresholds(cm, nchunk, nq, nchunk, k, false, b, b.th, st)))
+    return r;
+  HIPCHK(hipMemsetAsync(b.cnt, 0, (size_t)nq * 4, st));
+  KCHK(collect_ge(sc, (int)ldq, (int)nq, N, b.th, b.cnt, CAND_CAP, b.cs, b.ci, x->offset, st));
   const ExactRows xr = exact_rows(x);
-  KCHK(rescore_select((const float*)(w + o_cs), (const int64_t*)(w + o_ci), cnt, CAND_CAP, q32, qn, dim, xr.p,
-                      xr.f16, x->offset, RESCORE_MARGIN, nq, k, osc, oix, st));
+  KCHK(rescore_select(b.cs, b.ci, b.cnt, CAND_CAP, qs.q32, qs.qn, dim, xr.p, xr.f16, x->offset, RESCORE_MARGIN, nq, k,
+                      osc, oix, st));
   std::vector<int> hcnt(nq);
-  HIPCHK(hipMemcpyAsync(hcnt.data(), cnt, (size_t)nq * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(hipMemcpyAsync(hcnt.data(), b.cnt, (size_t)nq * 4, hipMemcpyDeviceToHost, st));
   HIPCHK(hipStreamSynchronize(st));
   // fewer than k candidates although the index holds k rows (nchunk >= k): scores that are NaN (a
   // zero or non-finite query; fewer than k rows with a finite norm) never pass score >= th, and
@@ -677,10 +756,10 @@ static int search_small(clm_index* x, const u16* q16, const float* qinv, const f
     } else if (hcnt[i] < k) {
       degenerate.push_back(i);
     }
-  x->search_stats[6] += nq - (int64_t)overflow.size() - (int64_t)degenerate.size();
-  x->search_stats[1] += (int64_t)degenerate.size();
+  x->search_stats[ST_SMALL] += nq - (int64_t)overflow.size() - (int64_t)degenerate.size();
+  x->search_stats[ST_EXACT_SCAN] += (int64_t)degenerate.size();
   if (overflow.empty() && degenerate.empty()) return CLM_OK;
-  return finish_overflow(x, overflow, ocount, q16, qinv, q32, qn, th, k, osc, oix, st, &degenerate);
+  return finish_overflow(x, overflow, ocount, qs, b.th, k, osc, oix, st, &degenerate);
 }
 
 // Top-k by EXACT cosine (the fp32-rounded fp64 cosine of the caller's query and rows), order
@@ -699,65 +778,82 @@ static int search_route(clm_index* x, const QueryStage& qs, int64_t nq, int k, f
   const int dim = (int)x->dim;
   const int64_t N = x->n;
   int r;
-  const char* e_full = getenv("CLM_SEARCH_FULL");
-  const char* e_exact = getenv("CLM_SEARCH_EXACT");
-  const char* e_bounded = getenv("CLM_SEARCH_BOUNDED");   // tests: bounded search at any size
-  const bool force_bounded = e_bounded && atoi(e_bounded) && N > 0;
+  const bool e_full = env_flag("CLM_SEARCH_FULL"), e_exact = env_flag("CLM_SEARCH_EXACT");
+  const bool force_bounded = env_flag("CLM_SEARCH_BOUNDED") && N > 0;   // tests: bounded search at any size
   // small batches on a large index: one streaming pass (search_small); $CLM_SEARCH_SMALLQ=1 takes
   // it at any size (tests), 0 never
-  const char* e_small = getenv("CLM_SEARCH_SMALLQ");
-  const int small_mode = e_small ? atoi(e_small) : -1;
+  const int64_t small_mode = env_int("CLM_SEARCH_SMALLQ", -1);
   const bool small = small_mode != 0 && k <= 1024 && N > 0 && search_small_fits(x, nq, k) &&
-                     (small_mode == 1 || (!force_bounded && !(e_full && atoi(e_full)) && !(e_exact && atoi(e_exact)) &&
-                                          N >= SMALL_MIN_ROWS));
+                     (small_mode == 1 || (!force_bounded && !e_full && !e_exact && N >= SMALL_MIN_ROWS));
   if (small) {
-    r = search_small(x, qs.q16, qs.qinv, qs.q32, qs.qn, nq, k, osc, oix, st);
+    r = search_small(x, qs, nq, k, osc, oix, st);
   } else if (k > 1024) {
     // any k: the exact scan over whole rows (topk_rows / the candidate lists stop at 1024)
     r = search_scan_large(x, qs.q32, qs.qn, nq, k, osc, oix, st);
-    x->search_stats[1] += nq;
-  } else if ((e_full && atoi(e_full)) || N == 0 || dim > MARGIN_MAX_DIM ||
+    x->search_stats[ST_EXACT_SCAN] += nq;
+  } else if (e_full || N == 0 || dim > MARGIN_MAX_DIM ||
              (!force_bounded && (double)nq * (double)N <= small_max)) {
     r = search_scan(x, true, qs.q16, qs.qinv, qs.q32, qs.qn, nq, k, osc, oix, st);
-    x->search_stats[1] += nq;
+    x->search_stats[ST_EXACT_SCAN] += nq;
   } else {
-    // sample of S rows: the k-th best of the sample ranks ~k * N / S = 256 in the index, so ~256
-    // candidates per query ($CLM_SAMPLE_DIV replaces the 256: A/B only)
-    static const int64_t sdiv = getenv("CLM_SAMPLE_DIV") ? std::max<int64_t>(16, atoll(getenv("CLM_SAMPLE_DIV"))) : 256;
-    const int64_t S = round_up(std::max<int64_t>(8192, (int64_t)k * N / sdiv), 256);
-    const bool sampled = !(e_exact && atoi(e_exact)) && k <= 256 && N >= 4 * S && S <= (1 << 18);
-    r = search_bounded(x, sampled, S, qs.q16, qs.qinv, qs.q32, qs.qn, nq, k, osc, oix, st);
+    // $CLM_SAMPLE_DIV replaces sample_size's 256: A/B only
+    static const int64_t sdiv = std::max<int64_t>(16, env_int("CLM_SAMPLE_DIV", 256));
+    const int64_t S = sample_size(k, N, sdiv);
+    const bool sampled = !e_exact && k <= 256 && N >= 4 * S && S <= (1 << 18);
+    r = search_bounded(x, sampled, S, qs, nq, k, osc, oix, st);
   }
   return r;
 }
 
+// every entry point's check of the query dtype (each keeps its own k range and messages)
+static int check_query_dtype(int q_dtype) {
+  return q_dtype == CLM_F32 || q_dtype == CLM_F16 ? CLM_OK : fail(CLM_E_ARG, "queries must be f32 or f16");
+}
+
+// Where a top-k call builds its results (osc / oix): the caller's arrays when both are on the
+// device, else two buffers taken from the Layout that sizes QueryStage::extra; bind() once the
+// queries are staged, finish() copies out (each array by where it lies) and drains the stream.
+struct ResultStage {
+  float* out_s; int64_t* out_i; size_t n; bool s_dev, i_dev, dev;
+  size_t o_s = 0, o_i = 0;
+  float* osc = nullptr; int64_t* oix = nullptr;
+  ResultStage(Layout& lay, float* out_scores, int64_t* out_idx, int64_t nq, int k)
+      : out_s(out_scores), out_i(out_idx), n((size_t)nq * k), s_dev(is_device_ptr(out_scores)),
+        i_dev(is_device_ptr(out_idx)), dev(s_dev && i_dev) {
+    if (!dev) { o_s = lay.take(n * 4); o_i = lay.take(n * 8); }
+  }
+  void bind(const QueryStage& qs) {
+    osc = dev ? out_s : (float*)(qs.extra + o_s);
+    oix = dev ? out_i : (int64_t*)(qs.extra + o_i);
+  }
+  int finish(hipStream_t st) const {
+    if (!dev) {
+      HIPCHK(hipMemcpyAsync(out_s, osc, n * 4, s_dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
+      HIPCHK(hipMemcpyAsync(out_i, oix, n * 8, i_dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, st));
+    }
+    HIPCHK(hipStreamSynchronize(st));   // workspaces are reused by the next call
+    return CLM_OK;
+  }
+};
+
 int clm_index_search(clm_index* x, const void* q, int q_dtype, int64_t nq, int k, float* out_scores,
                      int64_t* out_idx, void* stream) {
   if (!x || nq < 0 || (nq > 0 && (!q || !out_scores || !out_idx))) return fail(CLM_E_ARG, "bad argument");
-  if (q_dtype != CLM_F32 && q_dtype != CLM_F16) return fail(CLM_E_ARG, "queries must be f32 or f16");
+  if (int r = check_query_dtype(q_dtype)) return r;
   if (k < 1) return fail(CLM_E_ARG, "k must be >= 1");
   if (k > (1 << 26)) return fail(CLM_E_ARG, "k must be <= 2^26");
   if (nq == 0) return CLM_OK;
   DeviceGuard g(x->dev);
   hipStream_t st = (hipStream_t)stream;
-  const bool o_dev = is_device_ptr(out_scores) && is_device_ptr(out_idx);
-  Layout lay;   // the results' staging, when they go to the host
-  const size_t o_os = o_dev ? 0 : lay.take((size_t)nq * k * 4);
-  const size_t o_oi = o_dev ? 0 : lay.take((size_t)nq * k * 8);
+  Layout lay;
+  ResultStage res(lay, out_scores, out_idx, nq, k);
   QueryStage qs;
   int r = stage_queries(x, q, q_dtype, nq, lay.total(), st, &qs);
   if (!r) r = stage_queries_f16(x, qs, nq, st);
   if (r) return r;
-  float* osc = o_dev ? out_scores : (float*)(qs.extra + o_os);
-  int64_t* oix = o_dev ? out_idx : (int64_t*)(qs.extra + o_oi);
-  r = search_route(x, qs, nq, k, osc, oix, st);
-  if (r) return r;
-  if (!o_dev) {
-    HIPCHK(hipMemcpyAsync(out_scores, osc, (size_t)nq * k * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(out_idx, oix, (size_t)nq * k * 8, hipMemcpyDeviceToHost, st));
-  }
-  HIPCHK(hipStreamSynchronize(st));   // workspaces are reused by the next call
-  return CLM_OK;
+  res.bind(qs);
+  if ((r = search_route(x, qs, nq, k, res.osc, res.oix, st))) return r;
+  return res.finish(st);
 }
 
 // ---- filtered search (clm_index_search_masked) ----------------------------------------------
@@ -807,25 +903,27 @@ constexpr int64_t MASK_GATHER_DIV_SMALL = 8;
 // profiles/masked_search_ab.txt)
 constexpr double MASK_GATHER_SMALL = (double)(1 << 20);
 
-static int masked_exact(clm_index* x, const QueryStage& qs, int64_t nq, int k, const uint32_t* words, float* osc,
-                        int64_t* oix, hipStream_t st) {
-  int r = search_scan(x, true, nullptr, nullptr, qs.q32, qs.qn, nq, k, osc, oix, st, ScanFilter{words});
+// Route A of the filtered and the keyed search: the exact scan under the filter, dead entries' ids -> -1
+static int filtered_exact(clm_index* x, const float* q32, const double* qn, int64_t nq, int k, const RowFilter& allow,
+                          float* osc, int64_t* oix, hipStream_t st) {
+  int r = search_scan(x, true, nullptr, nullptr, q32, qn, nq, k, osc, oix, st, allow);
   if (r) return r;
   KCHK(map_ids(osc, oix, nq * k, nullptr, 0, st));
   return CLM_OK;
 }
 
-// queries `redo` of the batch served again by route A, their rows of osc / oix replaced
-static int masked_redo(clm_index* x, const QueryStage& qs, int k, const uint32_t* words,
-                       const std::vector<int64_t>& redo, float* osc, int64_t* oix, hipStream_t st) {
-  return redo_subset(x, redo, {{qs.q32, x->dim * 4}, {qs.qn, 8}}, {{osc, (int64_t)k * 4}, {oix, (int64_t)k * 8}},
-                     "masked redo", st, [&](void* const* in, void* const* out) -> int {
-                       int r = search_scan(x, true, nullptr, nullptr, (const float*)in[0], (const double*)in[1],
-                                           (int64_t)redo.size(), k, (float*)out[0], (int64_t*)out[1], st,
-                                           ScanFilter{words});
-                       if (r) return r;
-                       KCHK(map_ids((const float*)out[0], (int64_t*)out[1], (int64_t)redo.size() * k, nullptr, 0, st));
-                       return CLM_OK;
+// queries `redo` of the batch served again by route A, their rows of osc / oix replaced (a keyed
+// filter's ranges are gathered with the queries)
+static int filtered_redo(clm_index* x, const QueryStage& qs, int k, const RowFilter& allow,
+                         const std::vector<int64_t>& redo, float* osc, int64_t* oix, hipStream_t st) {
+  const std::initializer_list<RowArray> plain = {{qs.q32, x->dim * 4}, {qs.qn, 8}},
+                                        ranged = {{qs.q32, x->dim * 4}, {qs.qn, 8}, {allow.lo, 4}, {allow.hi, 4}};
+  return redo_subset(x, redo, allow.keys ? ranged : plain, {{osc, (int64_t)k * 4}, {oix, (int64_t)k * 8}},
+                     allow.keys ? "keyed redo" : "masked redo", st, [&](void* const* in, void* const* out) -> int {
+                       RowFilter sub = allow;
+                       if (allow.keys) { sub.lo = (const int32_t*)in[2]; sub.hi = (const int32_t*)in[3]; }
+                       return filtered_exact(x, (const float*)in[0], (const double*)in[1], (int64_t)redo.size(), k, sub,
+                                             (float*)out[0], (int64_t*)out[1], st);
                      });
 }
 
@@ -859,83 +957,72 @@ static int masked_gather(clm_index* x, const QueryStage& qs, int64_t nq, int k, 
                    : hipMemcpy2DAsync(last.data(), 8, oix + (need - 1), (size_t)k * 8, 8, (size_t)nq,
                                       hipMemcpyDeviceToHost, st);
   (void)hipStreamSynchronize(st);
-  // everything the routes allocated lazily in the temporary index (every device buffer of clm_index
-  // that is neither the gathered rows nor on loan: see the note at the struct)
-  for (void* p : {(void*)tmp.samp, (void*)tmp.samp_inv, (void*)tmp.inv_keys, tmp.ws, tmp.mut, (void*)tmp.res_s,
-                  (void*)tmp.res_i, (void*)tmp.rg_comp, (void*)tmp.rg_comp2, tmp.rg_items})
-    if (p) (void)hipFree(p);
+  // everything the routes allocated lazily in the temporary index: not the gathered rows (bufs owns
+  // them), not the workspaces on loan
+  index_free_buffers(&tmp, {tmp.rows, tmp.inv, tmp.rows32, tmp.ws2, tmp.ws3, tmp.ws4});
   if (r) return r;
   if (e != hipSuccess) return fail(CLM_E_HIP, std::string("masked search: ") + hipGetErrorString(e));
   std::vector<int64_t> redo;
   for (int64_t i = 0; i < nq && k <= 1024; ++i)
     if (last[i] < 0) redo.push_back(i);
   *n_redo = (int64_t)redo.size();
-  return masked_redo(x, qs, k, words, redo, osc, oix, st);
+  return filtered_redo(x, qs, k, RowFilter{words}, redo, osc, oix, st);
+}
+
+// The sampled thresholds and the candidate pass of the masked and the keyed search. The call's
+// sample -- S rows with inverse norms and, for a keyed filter, keys, which sample(s16, sinv, skeys)
+// fills -- is scored per query block, a keyed filter's closed entries are struck out, and th[q] =
+// its k-th best - RESCORE_MARGIN (fewer sample rows than k: no threshold, -inf). Then candidate_pass
+// under the filter; hcnt: every query's count, for the caller's rule of what is redone. The
+// sample-score rows are padded as search_bounded's.
+template <class Sample>
+static int filtered_pass(clm_index* x, const QueryStage& qs, int64_t nq, int k, const RowFilter& allow, int64_t S,
+                         float* osc, int64_t* oix, std::vector<int>& hcnt, hipStream_t st, Sample sample) {
+  const int dim = (int)x->dim;
+  int r;
+  const int64_t ldS = round_up(S, 4) + 64;
+  const int64_t nqb = band_query_block(nq, ldS * 4, 256);
+  Layout lay;
+  const size_t o_s16 = lay.take((size_t)S * dim * 2), o_si = lay.take((size_t)S * 4),
+               o_sk = allow.keys ? lay.take((size_t)S * 4) : 0, o_sc = lay.take((size_t)nqb * ldS * 4);
+  PassBufs b;
+  b.take(lay, nq, nqb, k);
+  if ((r = grow(&x->ws2, &x->ws2_bytes, lay.total()))) return r;
+  uint8_t* w = (uint8_t*)x->ws2;
+  b.bind(w);
+  u16* s16 = (u16*)(w + o_s16);
+  float* sinv = (float*)(w + o_si);
+  int32_t* skeys = allow.keys ? (int32_t*)(w + o_sk) : nullptr;
+  float* sc = (float*)(w + o_sc);
+  KCHK(sample(s16, sinv, skeys));
+  if (S < k) KCHK(fill_f32(b.th, nq, -INFINITY, st));
+  for (int64_t q0 = 0; q0 < nq && S >= k; q0 += nqb) {
+    const int64_t nb = std::min(nqb, nq - q0);
+    KCHK(sample_scores(qs, q0, nb, dim, s16, sinv, S, sc, ldS, 0, st));
+    // fewer than k open sample rows: the k-th value is a struck-out -inf, and so is theta
+    if (skeys) KCHK(key_fill(sc, ldS, nb, S, 0, skeys, allow.lo + q0, allow.hi + q0, st));
+    if ((r = row_thresholds(sc, ldS, nb, S, k, kth_one_pass(k), b, b.th + q0, st))) return r;
+  }
+  return candidate_pass(x, qs, nq, nqb, k, allow, b, osc, oix, hcnt, st, heuristic_cfg);
 }
 
 static int masked_pass(clm_index* x, const QueryStage& qs, int64_t nq, int k, const uint32_t* words,
                        const uint32_t* list, int64_t P, int64_t S, float* osc, int64_t* oix, int64_t* n_redo,
                        hipStream_t st) {
-  const int dim = (int)x->dim;
-  int r;
-  const int64_t ldS = round_up(S, 4) + 64;   // search_bounded's row padding
-  const int64_t nqb = band_query_block(nq, ldS * 4, 256);
-  Layout lay;
-  const size_t o_s16 = lay.take((size_t)S * dim * 2), o_si = lay.take((size_t)S * 4);
-  const size_t o_sc = lay.take((size_t)nqb * ldS * 4);
-  const size_t o_ts = lay.take((size_t)nqb * k * 4), o_ti = lay.take((size_t)nqb * k * 8);
-  const size_t o_th = lay.take((size_t)nq * 4), o_cnt = lay.take((size_t)nq * 4);
-  const size_t o_cs = lay.take((size_t)nqb * CAND_CAP * 4), o_ci = lay.take((size_t)nqb * CAND_CAP * 8);
-  if ((r = grow(&x->ws2, &x->ws2_bytes, lay.total()))) return r;
-  uint8_t* w = (uint8_t*)x->ws2;
-  u16* s16 = (u16*)(w + o_s16);
-  float* sinv = (float*)(w + o_si);
-  float* sc = (float*)(w + o_sc);
-  float* ts = (float*)(w + o_ts);
-  int64_t* ti = (int64_t*)(w + o_ti);
-  float* th = (float*)(w + o_th);
-  int* cnt = (int*)(w + o_cnt);
-  float* cs = (float*)(w + o_cs);
-  int64_t* ci = (int64_t*)(w + o_ci);
+  const RowFilter allow{words};
+  std::vector<int> hcnt;
   // the sample: S rows at positions floor(i * P / S) of the allowed list, in buffers of this call
-  KCHK(mask_gather(x->rows, nullptr, x->inv, dim, list, P, S, s16, nullptr, sinv, st));
-  if (S < k) KCHK(fill_f32(th, nq, -INFINITY, st));   // fewer sample rows than k: no threshold
-  for (int64_t q0 = 0; q0 < nq && S >= k; q0 += nqb) {
-    const int64_t nb = std::min(nqb, nq - q0);
-    GemmArgs ga{};
-    ga.A = qs.q16 + q0 * dim; ga.lda = dim; ga.W = s16; ga.ldw = dim;
-    ga.M = (int)nb; ga.N = (int)S; ga.K = dim; ga.out = sc; ga.ldo = ldS;
-    ga.rscale = qs.qinv + q0; ga.cscale = sinv;
-    KCHK(gemm(false, EPI_SCORE, ga, st));
-    if (k <= 8 && !g_kth_radix) {
-      KCHK(kth_thresholds(sc, ldS, nb, S, k, RESCORE_MARGIN, th + q0, st));
-    } else {
-      KCHK(topk_rows(sc, ldS, nb, S, k, 0, ts, ti, k, st));
-      KCHK(filter_thresholds(ts, k, nb, k, RESCORE_MARGIN, th + q0, st));
-    }
-  }
-  HIPCHK(hipMemsetAsync(cnt, 0, (size_t)nq * 4, st));
-  const ExactRows xr = exact_rows(x);
-  for (int64_t q0 = 0; q0 < nq; q0 += nqb) {
-    const int64_t nb = std::min(nqb, nq - q0);
-    GemmArgs gf = index_pass(x, qs.q16 + q0 * dim, qs.qinv + q0, nb, th + q0, cnt + q0, ci, CAND_CAP);
-    gf.cand_s = cs;
-    gf.cbound = inv_keys_of(x, st);
-    gf.mask = words;
-    KCHK(gemm_cfg(false, EPI_FILTER_MASK, -1, gf, st));
-    KCHK(rescore_select(cs, ci, cnt + q0, CAND_CAP, qs.q32 + q0 * dim, qs.qn + q0, dim, xr.p, xr.f16, x->offset,
-                        RESCORE_MARGIN, nb, k, osc + q0 * k, oix + q0 * k, st));
-  }
-  std::vector<int> hcnt(nq);
-  HIPCHK(hipMemcpyAsync(hcnt.data(), cnt, (size_t)nq * 4, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
+  int r = filtered_pass(x, qs, nq, k, allow, S, osc, oix, hcnt, st, [&](u16* s16, float* sinv, int32_t*) {
+    return mask_gather(x->rows, nullptr, x->inv, (int)x->dim, list, P, S, s16, nullptr, sinv, st);
+  });
+  if (r) return r;
   // an overflowed list, or one short of min(k, P) (NaN scores pass no threshold): route A decides
   std::vector<int64_t> redo;
   const int64_t need = std::min<int64_t>(k, P);
   for (int64_t i = 0; i < nq; ++i)
     if (hcnt[i] > CAND_CAP || hcnt[i] < need) redo.push_back(i);
   *n_redo = (int64_t)redo.size();
-  return masked_redo(x, qs, k, words, redo, osc, oix, st);
+  return filtered_redo(x, qs, k, allow, redo, osc, oix, st);
 }
 
 // The mask steps every filtered search starts with (clm_mask_rows runs them alone): the caller's words
@@ -956,31 +1043,30 @@ static int search_masked(clm_index* x, const QueryStage& qs, int64_t nq, int k, 
   const int64_t N = x->n, dim = x->dim;
   int r;
   if (P == 0) {   // nothing is allowed: (-inf, -1) lists (counted with the exact route)
-    x->search_stats[19] += nq;
+    x->search_stats[ST_MASK_EXACT] += nq;
     KCHK(fill_f32(osc, nq * k, -INFINITY, st));
     HIPCHK(hipMemsetAsync(oix, 0xFF, (size_t)nq * k * 8, st));
     return CLM_OK;
   }
-  const char* e_full = getenv("CLM_SEARCH_FULL");
   const bool exact_ok = k <= 1024;   // search_scan's lists
   // a zero or non-finite inverse norm: that row's scores are NaN, which the fp16 pass cannot list and
   // which the unmasked routes (the gather route's search) do not place above every number -- the
   // exact route does (mask_fill), so it serves such an index whenever its lists hold k
   bool fin = false;
   if ((r = inv_norms_finite(x, st, &fin))) return r;
-  const bool pass_ok = fin && k <= 256 && dim <= MARGIN_MAX_DIM && N <= 0x7FFFFFFF;
-  const int64_t Sd = round_up(std::max<int64_t>(8192, (int64_t)k * P / 256), 256);
+  const bool pass_ok = filter_pass_ok(x, fin, k);
+  const int64_t Sd = sample_size(k, P);
   enum { R_EXACT, R_GATHER, R_PASS } route;
   if (((flags & CLM_MASK_EXACT) || !fin) && exact_ok) route = R_EXACT;
   else if ((flags & CLM_MASK_PASS) && pass_ok) route = R_PASS;
   else if (flags & CLM_MASK_GATHER) route = R_GATHER;
-  else if (exact_ok && ((e_full && atoi(e_full)) || dim > MARGIN_MAX_DIM)) route = R_EXACT;
+  else if (exact_ok && (env_flag("CLM_SEARCH_FULL") || dim > MARGIN_MAX_DIM)) route = R_EXACT;
   else if (pass_ok && P >= 4 * Sd && Sd <= (1 << 18) && P * (nq <= 16 ? MASK_GATHER_DIV_SMALL : MASK_GATHER_DIV) > N)
     route = R_PASS;
   else route = R_GATHER;
   if (route == R_EXACT) {
-    x->search_stats[19] += nq;
-    return masked_exact(x, qs, nq, k, words, osc, oix, st);
+    x->search_stats[ST_MASK_EXACT] += nq;
+    return filtered_exact(x, qs.q32, qs.qn, nq, k, RowFilter{words}, osc, oix, st);
   }
   CallBufs bufs(st);
   uint32_t* list = (uint32_t*)bufs.take((size_t)P * 4);
@@ -989,20 +1075,20 @@ static int search_masked(clm_index* x, const QueryStage& qs, int64_t nq, int k, 
   int64_t n_redo = 0;
   if (route == R_GATHER) {
     r = masked_gather(x, qs, nq, k, words, list, P, osc, oix, &n_redo, st);
-    x->search_stats[18] += nq - n_redo;
-    x->search_stats[19] += n_redo;
+    x->search_stats[ST_MASK_GATHER] += nq - n_redo;
+    x->search_stats[ST_MASK_EXACT] += n_redo;
     return r;
   }
   r = masked_pass(x, qs, nq, k, words, list, P, std::min(std::min<int64_t>(Sd, 1 << 18), P), osc, oix, &n_redo, st);
-  x->search_stats[17] += nq - n_redo;
-  x->search_stats[19] += n_redo;
+  x->search_stats[ST_MASK_PASS] += nq - n_redo;
+  x->search_stats[ST_MASK_EXACT] += n_redo;
   return r;
 }
 
 int clm_index_search_masked(clm_index* x, const void* q, int q_dtype, int64_t nq, int k, const uint32_t* allow,
                             int flags, float* out_scores, int64_t* out_idx, void* stream) {
   if (!x || nq < 0 || (nq > 0 && (!q || !allow || !out_scores || !out_idx))) return fail(CLM_E_ARG, "bad argument");
-  if (q_dtype != CLM_F32 && q_dtype != CLM_F16) return fail(CLM_E_ARG, "queries must be f32 or f16");
+  if (int rc = check_query_dtype(q_dtype)) return rc;
   if (k < 1) return fail(CLM_E_ARG, "k must be >= 1");
   if (k > (1 << 26)) return fail(CLM_E_ARG, "k must be <= 2^26");
   if (x->n == 0) return fail(CLM_E_ARG, "masked search: the index is empty");
@@ -1010,10 +1096,9 @@ int clm_index_search_masked(clm_index* x, const void* q, int q_dtype, int64_t nq
   DeviceGuard g(x->dev);
   hipStream_t st = (hipStream_t)stream;
   const int64_t N = x->n, nw = mask_words(N), nblk = mask_blocks(N);
-  const bool o_dev = is_device_ptr(out_scores) && is_device_ptr(out_idx), a_dev = is_device_ptr(allow);
+  const bool a_dev = is_device_ptr(allow);
   Layout lay;   // the results' staging when they go to the host, then the mask's buffers
-  const size_t o_os = o_dev ? 0 : lay.take((size_t)nq * k * 4);
-  const size_t o_oi = o_dev ? 0 : lay.take((size_t)nq * k * 8);
+  ResultStage res(lay, out_scores, out_idx, nq, k);
   const size_t o_src = a_dev ? 0 : lay.take((size_t)nw * 4);
   const size_t o_words = lay.take((size_t)nw * 4), o_bcnt = lay.take((size_t)nblk * 4),
                o_boff = lay.take((size_t)(nblk + 1) * 8);
@@ -1021,8 +1106,7 @@ int clm_index_search_masked(clm_index* x, const void* q, int q_dtype, int64_t nq
   int r = stage_queries(x, q, q_dtype, nq, lay.total(), st, &qs);
   if (!r) r = stage_queries_f16(x, qs, nq, st);
   if (r) return r;
-  float* osc = o_dev ? out_scores : (float*)(qs.extra + o_os);
-  int64_t* oix = o_dev ? out_idx : (int64_t*)(qs.extra + o_oi);
+  res.bind(qs);
   const uint32_t* src = allow;
   if (!a_dev) {
     HIPCHK(copy_in(qs.extra + o_src, allow, (size_t)nw * 4, st));
@@ -1033,14 +1117,8 @@ int clm_index_search_masked(clm_index* x, const void* q, int q_dtype, int64_t nq
   int64_t* boff = (int64_t*)(qs.extra + o_boff);
   int64_t P = 0;
   if ((r = mask_plan(src, N, words, bcnt, boff, &P, st))) return r;
-  r = search_masked(x, qs, nq, k, words, boff, P, flags, osc, oix, st);
-  if (r) return r;
-  if (!o_dev) {
-    HIPCHK(copy_out(out_scores, osc, (size_t)nq * k * 4, st));
-    HIPCHK(copy_out(out_idx, oix, (size_t)nq * k * 8, st));
-  }
-  HIPCHK(hipStreamSynchronize(st));   // workspaces are reused by the next call
-  return CLM_OK;
+  if ((r = search_masked(x, qs, nq, k, words, boff, P, flags, res.osc, res.oix, st))) return r;
+  return res.finish(st);
 }
 
 int clm_mask_rows(int hip_device, const uint32_t* allow, int64_t N, uint32_t* words, uint32_t* bcnt, int64_t* boff,
@@ -1073,74 +1151,16 @@ int clm_mask_rows(int hip_device, const uint32_t* allow, int64_t N, uint32_t* wo
 //            EPI_FILTER_KEYS pass and rescore_select; a query whose list overflowed CAND_CAP or ended
 //            short of what its range holds is redone by route A. Nothing rests on the sample but speed.
 
-static int keyed_exact(clm_index* x, const float* q32, const double* qn, int64_t nq, int k, const int32_t* keys,
-                       const int32_t* lo, const int32_t* hi, float* osc, int64_t* oix, hipStream_t st) {
-  int r = search_scan(x, true, nullptr, nullptr, q32, qn, nq, k, osc, oix, st, ScanFilter{nullptr, keys, lo, hi});
-  if (r) return r;
-  KCHK(map_ids(osc, oix, nq * k, nullptr, 0, st));
-  return CLM_OK;
-}
-
 // hn_in: the caller's counts on the host, or null; hlo / hhi: the ranges on the host
-static int keyed_pass(clm_index* x, const QueryStage& qs, int64_t nq, int k, const int32_t* keys, const int32_t* lo,
-                      const int32_t* hi, const int32_t* hlo, const int32_t* hhi, const int64_t* hn_in, int64_t S,
-                      float* osc, int64_t* oix, int64_t* n_redo, hipStream_t st) {
-  const int dim = (int)x->dim;
-  int r;
-  const int64_t ldS = round_up(S, 4) + 64;   // search_bounded's row padding
-  const int64_t nqb = band_query_block(nq, ldS * 4, 256);
-  Layout lay;
-  const size_t o_s16 = lay.take((size_t)S * dim * 2), o_si = lay.take((size_t)S * 4), o_sk = lay.take((size_t)S * 4);
-  const size_t o_sc = lay.take((size_t)nqb * ldS * 4);
-  const size_t o_ts = lay.take((size_t)nqb * k * 4), o_ti = lay.take((size_t)nqb * k * 8);
-  const size_t o_th = lay.take((size_t)nq * 4), o_cnt = lay.take((size_t)nq * 4);
-  const size_t o_cs = lay.take((size_t)nqb * CAND_CAP * 4), o_ci = lay.take((size_t)nqb * CAND_CAP * 8);
-  if ((r = grow(&x->ws2, &x->ws2_bytes, lay.total()))) return r;
-  uint8_t* w = (uint8_t*)x->ws2;
-  u16* s16 = (u16*)(w + o_s16);
-  float* sinv = (float*)(w + o_si);
-  int32_t* skeys = (int32_t*)(w + o_sk);
-  float* sc = (float*)(w + o_sc);
-  float* ts = (float*)(w + o_ts);
-  int64_t* ti = (int64_t*)(w + o_ti);
-  float* th = (float*)(w + o_th);
-  int* cnt = (int*)(w + o_cnt);
-  float* cs = (float*)(w + o_cs);
-  int64_t* ci = (int64_t*)(w + o_ci);
+static int keyed_pass(clm_index* x, const QueryStage& qs, int64_t nq, int k, const RowFilter& allow, const int32_t* hlo,
+                      const int32_t* hhi, const int64_t* hn_in, int64_t S, float* osc, int64_t* oix, int64_t* n_redo,
+                      hipStream_t st) {
+  std::vector<int> hcnt;
   // the sample: S rows at positions floor(i * N / S) with their keys, in buffers of this call
-  KCHK(key_sample(x->rows, x->inv, keys, dim, x->n, S, s16, sinv, skeys, st));
-  if (S < k) KCHK(fill_f32(th, nq, -INFINITY, st));   // fewer sample rows than k: no threshold
-  for (int64_t q0 = 0; q0 < nq && S >= k; q0 += nqb) {
-    const int64_t nb = std::min(nqb, nq - q0);
-    GemmArgs ga{};
-    ga.A = qs.q16 + q0 * dim; ga.lda = dim; ga.W = s16; ga.ldw = dim;
-    ga.M = (int)nb; ga.N = (int)S; ga.K = dim; ga.out = sc; ga.ldo = ldS;
-    ga.rscale = qs.qinv + q0; ga.cscale = sinv;
-    KCHK(gemm(false, EPI_SCORE, ga, st));
-    KCHK(key_fill(sc, ldS, nb, S, 0, skeys, lo + q0, hi + q0, st));
-    // fewer than k open sample rows: the k-th value is a struck-out -inf, and so is theta
-    if (k <= 8 && !g_kth_radix) {
-      KCHK(kth_thresholds(sc, ldS, nb, S, k, RESCORE_MARGIN, th + q0, st));
-    } else {
-      KCHK(topk_rows(sc, ldS, nb, S, k, 0, ts, ti, k, st));
-      KCHK(filter_thresholds(ts, k, nb, k, RESCORE_MARGIN, th + q0, st));
-    }
-  }
-  HIPCHK(hipMemsetAsync(cnt, 0, (size_t)nq * 4, st));
-  const ExactRows xr = exact_rows(x);
-  for (int64_t q0 = 0; q0 < nq; q0 += nqb) {
-    const int64_t nb = std::min(nqb, nq - q0);
-    GemmArgs gf = index_pass(x, qs.q16 + q0 * dim, qs.qinv + q0, nb, th + q0, cnt + q0, ci, CAND_CAP);
-    gf.cand_s = cs;
-    gf.cbound = inv_keys_of(x, st);
-    gf.keys = keys; gf.klo = lo + q0; gf.khi = hi + q0;
-    KCHK(gemm_cfg(false, EPI_FILTER_KEYS, -1, gf, st));
-    KCHK(rescore_select(cs, ci, cnt + q0, CAND_CAP, qs.q32 + q0 * dim, qs.qn + q0, dim, xr.p, xr.f16, x->offset,
-                        RESCORE_MARGIN, nb, k, osc + q0 * k, oix + q0 * k, st));
-  }
-  std::vector<int> hcnt(nq);
-  HIPCHK(hipMemcpyAsync(hcnt.data(), cnt, (size_t)nq * 4, hipMemcpyDeviceToHost, st));
-  HIPCHK(hipStreamSynchronize(st));
+  int r = filtered_pass(x, qs, nq, k, allow, S, osc, oix, hcnt, st, [&](u16* s16, float* sinv, int32_t* skeys) {
+    return key_sample(x->rows, x->inv, allow.keys, (int)x->dim, x->n, S, s16, sinv, skeys, st);
+  });
+  if (r) return r;
   // an overflowed list, or one short of what the range holds (NaN scores pass no threshold; without
   // the caller's counts every list short of k): route A decides
   std::vector<int64_t> redo;
@@ -1152,13 +1172,7 @@ static int keyed_pass(clm_index* x, const QueryStage& qs, int64_t nq, int k, con
     if (hcnt[i] > CAND_CAP || hcnt[i] < std::min<int64_t>(k, open)) redo.push_back(i);
   }
   *n_redo = (int64_t)redo.size();
-  return redo_subset(x, redo, {{qs.q32, x->dim * 4}, {qs.qn, 8}, {lo, 4}, {hi, 4}},
-                     {{osc, (int64_t)k * 4}, {oix, (int64_t)k * 8}}, "keyed redo", st,
-                     [&](void* const* in, void* const* out) -> int {
-                       return keyed_exact(x, (const float*)in[0], (const double*)in[1], (int64_t)redo.size(), k, keys,
-                                          (const int32_t*)in[2], (const int32_t*)in[3], (float*)out[0],
-                                          (int64_t*)out[1], st);
-                     });
+  return filtered_redo(x, qs, k, allow, redo, osc, oix, st);
 }
 
 int clm_index_search_keyed(clm_index* x, const void* q, int q_dtype, int64_t nq, int k, const int32_t* keys,
@@ -1166,42 +1180,38 @@ int clm_index_search_keyed(clm_index* x, const void* q, int q_dtype, int64_t nq,
                            int64_t* out_idx, void* stream) {
   if (!x || nq < 0 || (nq > 0 && (!q || !keys || !lo || !hi || !out_scores || !out_idx)))
     return fail(CLM_E_ARG, "bad argument");
-  if (q_dtype != CLM_F32 && q_dtype != CLM_F16) return fail(CLM_E_ARG, "queries must be f32 or f16");
+  if (int rc = check_query_dtype(q_dtype)) return rc;
   if (k < 1 || k > 1024) return fail(CLM_E_ARG, "keyed search: 1 <= k <= 1024");
   if (flags & ~(CLM_MASK_EXACT | CLM_MASK_PASS)) return fail(CLM_E_ARG, "keyed search: flags are 0, CLM_MASK_EXACT or CLM_MASK_PASS");
   if (x->n == 0) return fail(CLM_E_ARG, "keyed search: the index is empty");
   if (nq == 0) return CLM_OK;
   DeviceGuard g(x->dev);
   hipStream_t st = (hipStream_t)stream;
-  const int64_t N = x->n, dim = x->dim;
-  const bool o_dev = is_device_ptr(out_scores) && is_device_ptr(out_idx);
+  const int64_t N = x->n;
   Layout lay;   // the results' staging when they go to the host, then the keys and the ranges
-  const size_t o_os = o_dev ? 0 : lay.take((size_t)nq * k * 4);
-  const size_t o_oi = o_dev ? 0 : lay.take((size_t)nq * k * 8);
+  ResultStage res(lay, out_scores, out_idx, nq, k);
   const size_t o_keys = lay.take((size_t)N * 4), o_lo = lay.take((size_t)nq * 4), o_hi = lay.take((size_t)nq * 4);
   QueryStage qs;
   int r = stage_queries(x, q, q_dtype, nq, lay.total(), st, &qs);
   if (r) return r;
-  float* osc = o_dev ? out_scores : (float*)(qs.extra + o_os);
-  int64_t* oix = o_dev ? out_idx : (int64_t*)(qs.extra + o_oi);
+  res.bind(qs);
   int32_t* dkeys = (int32_t*)(qs.extra + o_keys);
   int32_t* dlo = (int32_t*)(qs.extra + o_lo);
   int32_t* dhi = (int32_t*)(qs.extra + o_hi);
   HIPCHK(copy_in(dkeys, keys, (size_t)N * 4, st));
   HIPCHK(copy_in(dlo, lo, (size_t)nq * 4, st));
   HIPCHK(copy_in(dhi, hi, (size_t)nq * 4, st));
-  const char* e_full = getenv("CLM_SEARCH_FULL");
+  const RowFilter allow{nullptr, dkeys, dlo, dhi};
   // a zero or non-finite inverse norm: that row's scores are NaN, which only the exact route places
   // (see search_masked). Drains the stream: the copies above are done
   bool fin = false;
   if ((r = inv_norms_finite(x, st, &fin))) return r;
-  const int64_t Sd = round_up(std::max<int64_t>(8192, (int64_t)k * N / 256), 256);
-  const bool pass_ok = fin && k <= 256 && dim <= MARGIN_MAX_DIM && N <= 0x7FFFFFFF;
-  bool pass = pass_ok && !(flags & CLM_MASK_EXACT);
-  if (pass && !(flags & CLM_MASK_PASS)) pass = !(e_full && atoi(e_full)) && N >= 4 * Sd;
+  const int64_t Sd = sample_size(k, N);
+  bool pass = filter_pass_ok(x, fin, k) && !(flags & CLM_MASK_EXACT);
+  if (pass && !(flags & CLM_MASK_PASS)) pass = !env_flag("CLM_SEARCH_FULL") && N >= 4 * Sd;
   if (!pass) {
-    x->search_stats[21] += nq;
-    r = keyed_exact(x, qs.q32, qs.qn, nq, k, dkeys, dlo, dhi, osc, oix, st);
+    x->search_stats[ST_KEY_EXACT] += nq;
+    r = filtered_exact(x, qs.q32, qs.qn, nq, k, allow, res.osc, res.oix, st);
   } else {
     // the ranges and the caller's counts on the host: what each list must hold
     std::vector<int32_t> hlo(nq), hhi(nq);
@@ -1216,20 +1226,25 @@ int clm_index_search_keyed(clm_index* x, const void* q, int q_dtype, int64_t nq,
     HIPCHK(hipStreamSynchronize(st));
     if ((r = stage_queries_f16(x, qs, nq, st))) return r;
     int64_t n_redo = 0;
-    r = keyed_pass(x, qs, nq, k, dkeys, dlo, dhi, hlo.data(), hhi.data(), n_in ? hn.data() : nullptr,
-                   std::min(std::min<int64_t>(Sd, 1 << 18), N), osc, oix, &n_redo, st);
+    r = keyed_pass(x, qs, nq, k, allow, hlo.data(), hhi.data(), n_in ? hn.data() : nullptr,
+                   std::min(std::min<int64_t>(Sd, 1 << 18), N), res.osc, res.oix, &n_redo, st);
     if (!r) {
-      x->search_stats[20] += nq - n_redo;
-      x->search_stats[21] += n_redo;
+      x->search_stats[ST_KEY_PASS] += nq - n_redo;
+      x->search_stats[ST_KEY_EXACT] += n_redo;
     }
   }
   if (r) return r;
-  if (!o_dev) {
-    HIPCHK(copy_out(out_scores, osc, (size_t)nq * k * 4, st));
-    HIPCHK(copy_out(out_idx, oix, (size_t)nq * k * 8, st));
-  }
-  HIPCHK(hipStreamSynchronize(st));   // workspaces are reused by the next call
-  return CLM_OK;
+  return res.finish(st);
+}
+
+// Whether a whole rank / log-sum-exp / threshold call takes its exact route: asked for (force_exact:
+// the call's flag or $CLM_SEARCH_FULL=1), a zero or non-finite inverse norm in the index (!inv_ok),
+// rows the fp16-pass margins do not cover or the pass cannot number, or at most the 2^24 dot products
+// below which clm_index_search takes its exact scan too -- unless the fast route is asked for
+// (force_fast: the call's flag or, tests, $CLM_SEARCH_BOUNDED=1)
+static bool whole_call_exact(const clm_index* x, int64_t nq, bool inv_ok, bool force_exact, bool force_fast) {
+  return force_exact || !inv_ok || x->dim > MARGIN_MAX_DIM || x->n > 0x7FFFFFFF ||
+         (!force_fast && (double)nq * (double)x->n <= SMALL_PROBLEM);
 }
 
 // ---- exact retrieval ranks (clm_index_rank / clm_index_count_above) ------------------------
@@ -1303,7 +1318,7 @@ static int rank_band(clm_index* x, const unsigned* keys, const u16* q16, const f
   HIPCHK(hipStreamSynchronize(st));
   for (int64_t i = 0; i < nq; ++i) {
     if (hcnt[i] > cap) redo.push_back(i);
-    else x->search_stats[10] += hcnt[i];
+    else x->search_stats[ST_RANK_BAND_ROWS] += hcnt[i];
   }
   return CLM_OK;
 }
@@ -1319,7 +1334,7 @@ static int rank_band(clm_index* x, const unsigned* keys, const u16* q16, const f
 static int rank_run(clm_index* x, const void* q, int q_dtype, int64_t nq, const float* t_in, const int64_t* tgt,
                     int64_t* out_i, float* out_s, int band_cap, void* stream) {
   const bool is_rank = t_in == nullptr;
-  if (q_dtype != CLM_F32 && q_dtype != CLM_F16) return fail(CLM_E_ARG, "queries must be f32 or f16");
+  if (int rc = check_query_dtype(q_dtype)) return rc;
   if (x->n == 0) return fail(CLM_E_ARG, "the index is empty");
   if (nq == 0) return CLM_OK;
   DeviceGuard guard(x->dev);
@@ -1361,27 +1376,23 @@ static int rank_run(clm_index* x, const void* q, int q_dtype, int64_t nq, const 
   bool inv_ok = false;
   if ((r = inv_norms_finite(x, st, &inv_ok, &keys))) return r;
   const int flags = band_cap > 0 ? band_cap & (CLM_RANK_EXACT | CLM_RANK_BAND) : 0;
-  const char* e_full = getenv("CLM_SEARCH_FULL");
-  const char* e_bounded = getenv("CLM_SEARCH_BOUNDED");
-  const bool force_exact = (flags & CLM_RANK_EXACT) || (e_full && atoi(e_full));
-  const bool force_band = (flags & CLM_RANK_BAND) || (e_bounded && atoi(e_bounded));
-  const bool all_exact = force_exact || !inv_ok || dim > MARGIN_MAX_DIM || N > 0x7FFFFFFF ||
-                         (!force_band && (double)nq * (double)N <= (double)(1 << 24));
+  const bool all_exact = whole_call_exact(x, nq, inv_ok, (flags & CLM_RANK_EXACT) || env_flag("CLM_SEARCH_FULL"),
+                                         (flags & CLM_RANK_BAND) || env_flag("CLM_SEARCH_BOUNDED"));
   if (all_exact) {
     if ((r = rank_exact(x, q32, qn, t, g, nq, above, st))) return r;
-    x->search_stats[8] += nq;
+    x->search_stats[ST_RANK_EXACT] += nq;
   } else {
     if ((r = stage_queries_f16(x, qs, nq, st))) return r;
     const int64_t cap = band_capacity(band_cap, N);
     std::vector<int64_t> redo;
     if ((r = rank_band(x, keys, qs.q16, qs.qinv, q32, qn, t, g, nq, cap, above, redo, st))) return r;
-    x->search_stats[9] += (int64_t)redo.size();
+    x->search_stats[ST_RANK_OVERFLOW] += (int64_t)redo.size();
     std::vector<char> listed(nq, 0);
     for (int64_t i : redo) listed[i] = 1;
     for (int64_t i = 0; i < nq; ++i)
       if (!listed[i] && !(std::fabs(ht[i]) <= 3.4028235e38f)) redo.push_back(i);   // NaN or infinite t
-    x->search_stats[7] += nq - (int64_t)redo.size();
-    x->search_stats[8] += (int64_t)redo.size();
+    x->search_stats[ST_RANK_BAND] += nq - (int64_t)redo.size();
+    x->search_stats[ST_RANK_EXACT] += (int64_t)redo.size();
     // their queries, norms and targets gathered, one exact pass, counts scattered back
     r = redo_subset(x, redo, {{q32, (int64_t)dim * 4}, {qn, 8}, {t, 4}, {g, 8}}, {{above, 8}}, "rank", st,
                     [&](void* const* in, void* const* out) -> int {
@@ -1503,7 +1514,7 @@ static int lse_band(clm_index* x, const u16* q16, const float* qinv, const float
 int clm_index_lse(clm_index* x, const void* q, int q_dtype, int64_t nq, double scale, const float* head_floor,
                   double* out_lse, float* out_err, int band_cap, void* stream) {
   if (!x || nq < 0 || (nq > 0 && (!q || !out_lse))) return fail(CLM_E_ARG, "bad argument");
-  if (q_dtype != CLM_F32 && q_dtype != CLM_F16) return fail(CLM_E_ARG, "queries must be f32 or f16");
+  if (int rc = check_query_dtype(q_dtype)) return rc;
   if (!(scale > 0.0 && scale <= 1.7976931348623157e308)) return fail(CLM_E_ARG, "scale must be finite and positive");
   if (x->n == 0) return fail(CLM_E_ARG, "the index is empty");
   if (nq == 0) return CLM_OK;
@@ -1527,14 +1538,11 @@ int clm_index_lse(clm_index* x, const void* q, int q_dtype, int64_t nq, double s
   bool inv_ok = false;
   if ((r = inv_norms_finite(x, st, &inv_ok))) return r;
   const int flags = band_cap > 0 ? band_cap & (CLM_LSE_EXACT | CLM_LSE_FAST) : 0;
-  const char* e_full = getenv("CLM_SEARCH_FULL");
-  const bool force_exact = (flags & CLM_LSE_EXACT) || (e_full && atoi(e_full));
-  const bool force_fast = (flags & CLM_LSE_FAST) != 0;
-  const bool all_exact = force_exact || !inv_ok || dim > MARGIN_MAX_DIM || N > 0x7FFFFFFF || !head_floor ||
-                         (!force_fast && (double)nq * (double)N <= (double)(1 << 24));
+  const bool all_exact = !head_floor || whole_call_exact(x, nq, inv_ok, (flags & CLM_LSE_EXACT) || env_flag("CLM_SEARCH_FULL"),
+                                                        (flags & CLM_LSE_FAST) != 0);
   if (all_exact) {
     if ((r = lse_exact(x, q32, qn, nq, scale, lse, err, st))) return r;
-    x->search_stats[12] += nq;
+    x->search_stats[ST_LSE_EXACT] += nq;
   } else {
     HIPCHK(copy_in(theta, head_floor, (size_t)nq * 4, st));
     if ((r = stage_queries_f16(x, qs, nq, st))) return r;
@@ -1542,9 +1550,9 @@ int clm_index_lse(clm_index* x, const void* q, int q_dtype, int64_t nq, double s
     std::vector<int64_t> todo;
     int64_t overflowed = 0;
     if ((r = lse_band(x, qs.q16, qs.qinv, q32, qn, theta, nq, cap, scale, lse, err, redo, todo, overflowed, st))) return r;
-    x->search_stats[13] += overflowed;
-    x->search_stats[11] += nq - (int64_t)todo.size();
-    x->search_stats[12] += (int64_t)todo.size();
+    x->search_stats[ST_LSE_OVERFLOW] += overflowed;
+    x->search_stats[ST_LSE_FAST] += nq - (int64_t)todo.size();
+    x->search_stats[ST_LSE_EXACT] += (int64_t)todo.size();
     // their queries and norms gathered, one exact pass, results scattered back
     r = redo_subset(x, todo, {{q32, (int64_t)dim * 4}, {qn, 8}}, {{lse, 8}, {err, 4}}, "lse", st,
                     [&](void* const* in, void* const* out) -> int {
@@ -1564,7 +1572,7 @@ int clm_index_lse(clm_index* x, const void* q, int q_dtype, int64_t nq, double s
 int clm_index_lse64(clm_index* x, const void* q, int q_dtype, int64_t nq, double scale, const int64_t* target,
                     double* out_lse, double* out_pair, void* stream) {
   if (!x || nq < 0 || (nq > 0 && (!q || !out_lse || (out_pair && !target)))) return fail(CLM_E_ARG, "bad argument");
-  if (q_dtype != CLM_F32 && q_dtype != CLM_F16) return fail(CLM_E_ARG, "queries must be f32 or f16");
+  if (int rc = check_query_dtype(q_dtype)) return rc;
   if (!(scale > 0.0 && scale <= 1.7976931348623157e308)) return fail(CLM_E_ARG, "scale must be finite and positive");
   if (x->n == 0) return fail(CLM_E_ARG, "the index is empty");
   if (nq == 0) return CLM_OK;
@@ -1583,7 +1591,7 @@ int clm_index_lse64(clm_index* x, const void* q, int q_dtype, int64_t nq, double
     HIPCHK(hipMemsetAsync(pair, 0xFF, (size_t)nq * 8, st));   // NaN: a target outside the index keeps it
   }
   if ((r = lse_exact(x, qs.q32, qs.qn, nq, scale, lse, nullptr, st, true, tg, pair))) return r;
-  x->search_stats[12] += nq;
+  x->search_stats[ST_LSE_EXACT] += nq;
   HIPCHK(copy_out(out_lse, lse, (size_t)nq * 8, st));
   if (pair) HIPCHK(copy_out(out_pair, pair, (size_t)nq * 8, st));
   HIPCHK(hipStreamSynchronize(st));   // workspaces are reused by the next call
@@ -1769,7 +1777,7 @@ static int range_band(clm_index* x, const unsigned* keys, const QueryStage& qs, 
   std::vector<int64_t> wide;
   int64_t cap_max = 0;
   for (size_t j = 0; j < over.size(); ++j) {
-    const int64_t cap2 = std::min<int64_t>(N, ocount[j] + ocount[j] / 8 + 256);
+    const int64_t cap2 = std::min<int64_t>(N, wide_capacity(ocount[j]));
     if (cap2 * 12 <= ((int64_t)1 << 30)) {
       wide.push_back(over[j]);
       cap_max = std::max(cap_max, cap2);
@@ -1778,36 +1786,18 @@ static int range_band(clm_index* x, const unsigned* keys, const QueryStage& qs, 
     }
   }
   if (wide.empty()) return CLM_OK;
-  const int64_t n = (int64_t)wide.size();
-  const int64_t G = std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(n, 4096), ((int64_t)1 << 30) / (cap_max * 12)));
-  Layout lay;
-  const size_t p_x = lay.take((size_t)G * 8), p_q16 = lay.take((size_t)G * dim * 2), p_qi = lay.take((size_t)G * 4),
-               p_q32 = lay.take((size_t)G * dim * 4), p_qn = lay.take((size_t)G * 8), p_th = lay.take((size_t)G * 4),
-               p_tau = lay.take((size_t)G * 4);
   RangeBufs b;
-  b.take(lay, G, cap_max);
-  if ((r = grow(&x->ws4, &x->ws4_bytes, lay.total()))) return r;
-  uint8_t* w = (uint8_t*)x->ws4;
-  int64_t* gx = (int64_t*)(w + p_x);
-  for (int64_t g0 = 0; g0 < n; g0 += G) {
-    const int64_t ng = std::min(G, n - g0);
-    HIPCHK(hipMemcpyAsync(gx, wide.data() + g0, (size_t)ng * 8, hipMemcpyHostToDevice, st));
-    KCHK(gather_rows(qs.q16, (int64_t)dim * 2, gx, ng, (int64_t)dim * 2, w + p_q16, (int64_t)dim * 2, false, st));
-    KCHK(gather_rows(qs.qinv, 4, gx, ng, 4, w + p_qi, 4, false, st));
-    KCHK(gather_rows(qs.q32, (int64_t)dim * 4, gx, ng, (int64_t)dim * 4, w + p_q32, (int64_t)dim * 4, false, st));
-    KCHK(gather_rows(qs.qn, 8, gx, ng, 8, w + p_qn, 8, false, st));
-    KCHK(gather_rows(theta, 4, gx, ng, 4, w + p_th, 4, false, st));
-    KCHK(gather_rows(tau, 4, gx, ng, 4, w + p_tau, 4, false, st));
-    // these lists overflowed: appends dominate the pass, gemm_kernel's 256 x 256 FILTER epilogue
-    // (overflow_wide's choice)
-    static const int ocfg = getenv("CLM_GEMM_CFG") ? -1 : 1;
-    std::vector<int64_t> ocount2;
-    if ((r = range_pass(x, keys, (const u16*)(w + p_q16), (const float*)(w + p_qi), (const float*)(w + p_q32),
-                        (const double*)(w + p_qn), (const float*)(w + p_tau), (const float*)(w + p_th), ng, cap_max,
-                        ocfg, w, b, wide.data() + g0, rb, exact, ocount2, st)))
-      return r;   // range_pass drains the stream: gx may be rewritten
-  }
-  return CLM_OK;
+  return wide_groups(   // gathered: in[0] = q16, [1] = qinv, [2] = q32, [3] = qn, [4] = theta, [5] = tau
+      x, wide, cap_max,
+      {{qs.q16, (int64_t)dim * 2}, {qs.qinv, 4}, {qs.q32, (int64_t)dim * 4}, {qs.qn, 8}, {theta, 4}, {tau, 4}}, st,
+      [&](Layout& lay, int64_t G) { b.take(lay, G, cap_max); },
+      [&](uint8_t* w, void* const* in, const int64_t*, int64_t g0, int64_t ng) -> int {
+        // these lists overflowed: dense_cfg, overflow_wide's choice. range_pass drains the stream
+        std::vector<int64_t> ocount2;
+        return range_pass(x, keys, (const u16*)in[0], (const float*)in[1], (const float*)in[2], (const double*)in[3],
+                          (const float*)in[5], (const float*)in[4], ng, cap_max, dense_cfg(), w, b, wide.data() + g0, rb,
+                          exact, ocount2, st);
+      });
 }
 
 // Segmented sort of the placed segments and the decode into the held result, in CSR order.
@@ -1909,7 +1899,7 @@ static int range_finish(clm_index* x, const RangeBuild& rb, int64_t nq, int64_t*
 // fp16 pass never lists).
 static int range_run(clm_index* x, const void* q, int q_dtype, int64_t nq, const float* threshold,
                      int64_t* out_offsets, int band_cap, void* stream) {
-  if (q_dtype != CLM_F32 && q_dtype != CLM_F16) return fail(CLM_E_ARG, "queries must be f32 or f16");
+  if (int rc = check_query_dtype(q_dtype)) return rc;
   if (x->n == 0) return fail(CLM_E_ARG, "the index is empty");
   if (x->n > 0xFFFFFFFFll) return fail(CLM_E_ARG, "threshold search: at most 2^32 - 1 rows per index");
   DeviceGuard guard(x->dev);
@@ -1941,12 +1931,8 @@ static int range_run(clm_index* x, const void* q, int q_dtype, int64_t nq, const
   bool inv_ok = false;
   if ((r = inv_norms_finite(x, st, &inv_ok, &keys))) return r;   // drains the stream
   const int flags = band_cap > 0 ? band_cap & (CLM_RANK_EXACT | CLM_RANK_BAND) : 0;
-  const char* e_full = getenv("CLM_SEARCH_FULL");
-  const char* e_bounded = getenv("CLM_SEARCH_BOUNDED");
-  const bool force_exact = (flags & CLM_RANK_EXACT) || (e_full && atoi(e_full));
-  const bool force_band = (flags & CLM_RANK_BAND) || (e_bounded && atoi(e_bounded));
-  const bool all_exact = force_exact || !inv_ok || dim > MARGIN_MAX_DIM || N > 0x7FFFFFFF ||
-                         (!force_band && (double)nq * (double)N <= (double)(1 << 24));
+  const bool all_exact = whole_call_exact(x, nq, inv_ok, (flags & CLM_RANK_EXACT) || env_flag("CLM_SEARCH_FULL"),
+                                         (flags & CLM_RANK_BAND) || env_flag("CLM_SEARCH_BOUNDED"));
   int64_t n_fast = 0, n_exact = nq, n_over = 0;
   if (all_exact) {
     if ((r = range_exact(x, qs.q32, qs.qn, tau, nq, nullptr, rb, st))) return r;
@@ -1975,9 +1961,9 @@ static int range_run(clm_index* x, const void* q, int q_dtype, int64_t nq, const
     if (r) return r;
   }
   if ((r = range_finish(x, rb, nq, out_offsets, st))) return r;
-  x->search_stats[14] += n_fast;
-  x->search_stats[15] += n_exact;
-  x->search_stats[16] += n_over;
+  x->search_stats[ST_RANGE_FAST] += n_fast;
+  x->search_stats[ST_RANGE_EXACT] += n_exact;
+  x->search_stats[ST_RANGE_OVERFLOW] += n_over;
   return CLM_OK;
 }
 
@@ -2014,5 +2000,3 @@ int clm_index_search_above_read(clm_index* x, int64_t start, int64_t n, float* o
   HIPCHK(hipStreamSynchronize(st));
   return CLM_OK;
 }
-
-}  // extern "C"
