@@ -8,7 +8,8 @@ from .config import ModelConfig, TowerConfig, PRESETS, get_preset  # noqa: F401
 
 # the retrieval evaluator (evaluate.py), loaded on first use: importing the package stays light
 _EVALUATE = ("retrieval_ranks", "recall_at_k", "mrr", "mean_average_precision", "evaluate_retrieval",
-             "matching_accuracy", "contrastive_loss", "CLIPEvaluator")
+             "matching_accuracy", "contrastive_loss", "CLIPEvaluator", "contrastive_loss_grad",
+             "contrastive_loss_tensor", "ContrastiveLoss")
 
 __all__ = ["ModelConfig", "TowerConfig", "PRESETS", "get_preset", *_EVALUATE]
 

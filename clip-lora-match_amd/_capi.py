@@ -97,6 +97,13 @@ def lib():
                                   c_void_p]),
         "clm_index_lse64": (c_int, [c_void_p, c_void_p, c_int, c_int64, ctypes.c_double, c_void_p, c_void_p, c_void_p,
                                     c_void_p]),
+        "clm_index_softmax_grad": (c_int, [c_void_p, c_void_p, c_int, c_int64, ctypes.c_double, c_void_p, c_void_p,
+                                           ctypes.c_double, ctypes.c_double, c_void_p, c_void_p, c_int64, c_int64,
+                                           c_void_p]),
+        "clm_gemm_softw": (c_int, [c_int, c_int, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int, c_void_p,
+                                   c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int64, c_void_p]),
+        "clm_transpose16": (c_int, [c_int, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_int64,
+                                    c_void_p]),
         "clm_index_search_above": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_int, c_void_p]),
         "clm_index_search_above_rows": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int, c_void_p]),
         "clm_index_search_above_read": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
@@ -197,11 +204,14 @@ EXPORTED = (
     "clm_gemm_select", "clm_value_bounds",
     "clm_topk_any", "clm_mask_rows", "clm_topk_distinct",
     "clm_index_search_keyed", "clm_gemm_select_keyed",
+    "clm_index_softmax_grad", "clm_gemm_softw", "clm_transpose16",
 )
 CLM_EPI_STORE, CLM_EPI_GELU, CLM_EPI_RESID, CLM_EPI_SCORE = 0, 1, 2, 4
 CLM_EPI_PATCH = 3   # clm_gemm_ex only
 CLM_EPI_FILTER, CLM_EPI_RANK, CLM_EPI_LSE, CLM_EPI_FILTER_MASK = 5, 6, 7, 8   # clm_gemm_select only
 CLM_EPI_FILTER_KEYS = 9   # clm_gemm_select_keyed only
+CLM_EPI_SOFTW = 10   # clm_gemm_softw only
+SOFTW_CONFIGS = (0, 1)   # the tile configs EPI_SOFTW is instantiated on (k_gemm.hip launch_softw)
 CLM_PROF_GEMM, CLM_PROF_ATTN, CLM_PROF_LN, CLM_PROF_OTHER = 0, 1, 2, 3
 
 

@@ -95,6 +95,8 @@ enum SearchStat {
   ST_MASK_PASS, ST_MASK_GATHER, ST_MASK_EXACT,
   // keyed-search queries served by the pass route / the exact route (a redone query counts in the latter)
   ST_KEY_PASS, ST_KEY_EXACT,
+  // softmax-gradient queries served, and the (query block, row chunk) passes run for them
+  ST_GRAD_QUERIES, ST_GRAD_PASSES,
   ST_COUNT
 };
 

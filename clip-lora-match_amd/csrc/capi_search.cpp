@@ -1,5 +1,6 @@
 // libclm C-ABI, searching the resident index: clm_index_search and its routes, the filtered, keyed
-// and threshold searches, exact retrieval ranks and the streaming log-sum-exp, after the plumbing
+// and threshold searches, exact retrieval ranks, the streaming log-sum-exp and (last) the streaming
+// softmax gradients with their two test hooks, after the plumbing
 // they share: query staging (QueryStage), band query blocks, the exact routes' row windows, redoing
 // a subset of the queries exactly (redo_subset), the overflowed lists' gathered groups (wide_groups);
 // further down one row filter (RowFilter), one candidate pass (PassBufs, row_thresholds,
@@ -1998,5 +1999,207 @@ int clm_index_search_above_read(clm_index* x, int64_t start, int64_t n, float* o
   HIPCHK(copy_out(out_scores, x->res_s + start, (size_t)n * 4, st));
   HIPCHK(copy_out(out_idx, x->res_i + start, (size_t)n * 8, st));
   HIPCHK(hipStreamSynchronize(st));
+  return CLM_OK;
+}
+
+// ---- streaming softmax gradients (clm_index_softmax_grad) -------------------------------------
+// dq[i] = sum_j W_ij r^_j and dr[j] = sum_i W_ij q^_i with W_ij = wq exp(scale s_ij - q_lse[i]) + wr
+// exp(scale s_ij - row_lse[j]) over the fp16-pass scores, per (row chunk, query block): the EPI_SOFTW
+// GEMM writes the block's fp16 weights W16 [nb, C], transpose16 gives W16T [C, nb], and the two fp16
+// GEMMs accumulate in fp32 into the outputs (EPI_RESID, or gemm_splitk_resid where the tiles are short
+// of a round of the CUs). Their other operands are K-contiguous transposes made once per chunk / per
+// call with the inverse norms folded in: R^T [dim, C] and Q^T [dim, nq]. Chunks outside, blocks inside:
+// every output element is added to by launches in stream order, and no kernel uses a floating-point
+// atomic, so a call's bits are a function of its arguments.
+//
+// Scaling: with a = wq / wmax, b = wr / wmax (wmax the larger weight) a stored weight is
+// 2^p (a exp(..) + b exp(..)); an exponential is at most exp(2 scale E) for offsets within scale E of
+// the true log-sum-exps (the fp16-pass score adds the other scale E), so 2^p = 65504 / ((a + b) exp(2
+// scale E)) puts the largest possible weight on the largest fp16 and every weight above 2^-14 / 65504
+// = 9.3e-10 of it in fp16's normal range. log2 a + p and log2 b + p go into the offset arrays, wmax 2^-p
+// multiplies the fp32 results.
+constexpr int64_t GRAD_CHUNK_ROWS = 4096;    // default C (profiles/loss_grad_ab.txt)
+constexpr int64_t GRAD_QUERY_BLOCK = 32768;  // default cap of B
+
+// K slices of an accumulating GEMM [M, N] (0: the plain EPI_RESID GEMM): its 128 x 128 tiles short of
+// half the CUs' 2-per-CU slots, the largest divisor of K / 64 up to 8; $CLM_GRAD_SLICES overrides (A/B)
+static int grad_slices(int64_t M, int64_t N, int64_t K) {
+  static const int64_t forced = env_int("CLM_GRAD_SLICES", -1);
+  const int64_t ksteps = K / 64;
+  int64_t want = 8;
+  if (forced >= 0) want = forced;
+  else if (((M + 127) / 128) * ((N + 127) / 128) >= 256) return 0;
+  for (int64_t s = std::min<int64_t>(want, ksteps); s >= 2; --s)
+    if (ksteps % s == 0) return (int)s;
+  return 0;
+}
+
+// out[M, N] += A[M, K] . W[N, K]^T, fp16 operands, fp32 accumulation into out (ldo = N)
+static int grad_accumulate(const u16* A, int64_t lda, const u16* W, int64_t ldw, int64_t M, int64_t N, int64_t K,
+                           float* out, int slices, float* part, hipStream_t st) {
+  GemmArgs g{};
+  g.A = A; g.lda = lda; g.W = W; g.ldw = ldw; g.M = (int)M; g.N = (int)N; g.K = (int)K;
+  g.out = out; g.ldo = N;
+  if (slices >= 2) KCHK(gemm_splitk_resid(false, g, slices, part, st));
+  else KCHK(gemm(false, EPI_RESID, g, st));
+  return CLM_OK;
+}
+
+int clm_index_softmax_grad(clm_index* x, const void* q, int q_dtype, int64_t nq, double scale, const double* q_lse,
+                           const double* row_lse, double wq, double wr, float* out_dq, float* out_dr,
+                           int64_t chunk_rows, int64_t query_block, void* stream) {
+  if (!x || nq < 0 || chunk_rows < 0 || query_block < 0 || (nq > 0 && (!q || !q_lse)))
+    return fail(CLM_E_ARG, "bad argument");
+  if (int rc = check_query_dtype(q_dtype)) return rc;
+  if (!(scale > 0.0 && scale <= 1.7976931348623157e308)) return fail(CLM_E_ARG, "scale must be finite and positive");
+  if (!(wq >= 0.0 && wq <= 1.7976931348623157e308) || !(wr >= 0.0 && wr <= 1.7976931348623157e308))
+    return fail(CLM_E_ARG, "the weights must be finite and not negative");
+  if (wr > 0.0 && !row_lse) return fail(CLM_E_ARG, "wr > 0 needs row_lse");
+  if (x->n == 0) return fail(CLM_E_ARG, "the index is empty");
+  if (x->dim > MARGIN_MAX_DIM) return fail(CLM_E_ARG, "softmax_grad: dim > 8192 is outside the fp16 pass's bound");
+  if (x->n > 0x7FFFFFFF) return fail(CLM_E_ARG, "softmax_grad: more than 2^31 - 1 rows");
+  if (nq == 0) return CLM_OK;
+  DeviceGuard guard(x->dev);
+  hipStream_t st = (hipStream_t)stream;
+  const int dim = (int)x->dim;
+  const int64_t N = x->n;
+  const bool use_r = row_lse && wr > 0.0;
+
+  Layout ql;
+  const size_t o_lse = ql.take((size_t)nq * 8), o_lq = ql.take((size_t)nq * 4);
+  QueryStage qs;
+  int r = stage_queries(x, q, q_dtype, nq, ql.total(), st, &qs);
+  if (r) return r;
+  double* lse_d = (double*)(qs.extra + o_lse);
+  float* lq = (float*)(qs.extra + o_lq);
+  HIPCHK(copy_in(lse_d, q_lse, (size_t)nq * 8, st));
+  if ((r = stage_queries_f16(x, qs, nq, st))) return r;
+  std::vector<double> hqn((size_t)nq);
+  HIPCHK(hipMemcpyAsync(hqn.data(), qs.qn, (size_t)nq * 8, hipMemcpyDeviceToHost, st));
+  bool inv_ok = false;
+  if ((r = inv_norms_finite(x, st, &inv_ok))) return r;   // drains the stream: hqn is here too
+  if (!inv_ok) return fail(CLM_E_ARG, "softmax_grad: the index holds a row whose norm is zero or not finite");
+  for (int64_t i = 0; i < nq; ++i)
+    if (!(hqn[i] > 0.0 && hqn[i] <= 1.7976931348623157e308))
+      return fail(CLM_E_ARG, "softmax_grad: query " + std::to_string(i) + " has a zero or non-finite norm");
+
+  // blocks and chunks: multiples of 64 (the GEMMs' K granule and the operands' 16-byte alignment)
+  const int64_t nqp = round_up(nq, 64);
+  int64_t C = std::min(round_up(chunk_rows > 0 ? chunk_rows : GRAD_CHUNK_ROWS, 64), round_up(N, 64));
+  int64_t B = std::min(round_up(query_block > 0 ? query_block : GRAD_QUERY_BLOCK, 64), nqp);
+  if (query_block == 0) {   // the two W buffers within the workspace budget (band_query_block's rule)
+    size_t fr = 0, tot = 0;
+    int64_t cap_b = env_int("CLM_SEARCH_WS_MB", 8192) << 20;
+    if (hipMemGetInfo(&fr, &tot) == hipSuccess) cap_b = std::min<int64_t>(cap_b, (int64_t)(fr / 4));
+    else (void)hipGetLastError();
+    const int64_t fit = cap_b / (C * 2 * (out_dr ? 2 : 1)) / 64 * 64;
+    B = std::max<int64_t>(64, std::min(B, fit));
+  }
+  const bool dq_direct = out_dq && is_device_ptr(out_dq), dr_direct = out_dr && is_device_ptr(out_dr);
+  const int sl_q = out_dq ? grad_slices(B, dim, C) : 0, sl_r = out_dr ? grad_slices(C, dim, B) : 0;
+  Layout lay;
+  const size_t o_rlse = lay.take(use_r ? (size_t)N * 8 : 0), o_lr = lay.take(use_r ? (size_t)N * 4 : 0),
+               o_qt = lay.take(out_dr ? (size_t)dim * nqp * 2 : 0), o_rt = lay.take(out_dq ? (size_t)dim * C * 2 : 0),
+               o_w = lay.take((size_t)B * C * 2), o_wt = lay.take(out_dr ? (size_t)C * B * 2 : 0),
+               o_dq = lay.take(out_dq && !dq_direct ? (size_t)nq * dim * 4 : 0),
+               o_dr = lay.take(out_dr && !dr_direct ? (size_t)C * dim * 4 : 0),
+               o_part = lay.take(std::max(sl_q ? gemm_splitk_ws_bytes((int)B, dim, sl_q) : 0,
+                                          sl_r ? gemm_splitk_ws_bytes((int)C, dim, sl_r) : 0));
+  if ((r = grow(&x->ws2, &x->ws2_bytes, lay.total()))) return r;
+  uint8_t* w = (uint8_t*)x->ws2;
+  float* lr = use_r ? (float*)(w + o_lr) : nullptr;
+  u16 *QT = (u16*)(w + o_qt), *RT = (u16*)(w + o_rt), *W16 = (u16*)(w + o_w), *W16T = (u16*)(w + o_wt);
+  float* dq = !out_dq ? nullptr : dq_direct ? out_dq : (float*)(w + o_dq);
+  float* part = (float*)(w + o_part);
+
+  const double a = use_r && wr > wq ? wq / wr : 1.0, b = !use_r ? 0.0 : wr > wq ? 1.0 : wr / wq;
+  const double wmax = use_r && wr > wq ? wr : wq;
+  if (wmax == 0.0) {   // no weight at all: the sums are zero
+    if (dq_direct) HIPCHK(hipMemsetAsync(out_dq, 0, (size_t)nq * dim * 4, st));
+    else if (out_dq) std::memset(out_dq, 0, (size_t)nq * dim * 4);
+    if (dr_direct) HIPCHK(hipMemsetAsync(out_dr, 0, (size_t)N * dim * 4, st));
+    else if (out_dr) std::memset(out_dr, 0, (size_t)N * dim * 4);
+    HIPCHK(hipStreamSynchronize(st));
+    return CLM_OK;
+  }
+  const double p = std::log2(65504.0) - std::log2(a + b) - 2.0 * scale * LSE_E * 1.4426950408889634;
+  const float unscale = (float)(wmax * std::exp2(-p));
+  // log2(0) = -inf makes the offsets of an absent term +inf: exp2(x - inf) = 0
+  KCHK(softw_offsets(lse_d, nq, std::log2(a) + p, lq, st));
+  if (use_r) {
+    HIPCHK(copy_in(w + o_rlse, row_lse, (size_t)N * 8, st));
+    KCHK(softw_offsets((const double*)(w + o_rlse), N, std::log2(b) + p, lr, st));
+  }
+  // every weight ever stored is finite (EPI_SOFTW clamps): zeros first, so the columns between a
+  // ragged chunk's end and its K granule multiply the transposes' zero padding with finite values
+  HIPCHK(hipMemsetAsync(W16, 0, (size_t)B * C * 2, st));
+  if (out_dr) KCHK(transpose16(qs.q16, dim, nq, dim, qs.qinv, QT, nqp, st));
+  if (out_dq) HIPCHK(hipMemsetAsync(dq, 0, (size_t)nq * dim * 4, st));
+
+  int64_t passes = 0;
+  for (int64_t r0 = 0; r0 < N; r0 += C) {
+    const int64_t cn = std::min(C, N - r0), ck = round_up(cn, 64);
+    float* drc = !out_dr ? nullptr : dr_direct ? out_dr + r0 * dim : (float*)(w + o_dr);
+    if (out_dr) HIPCHK(hipMemsetAsync(drc, 0, (size_t)cn * dim * 4, st));
+    if (out_dq) KCHK(transpose16(x->rows + r0 * dim, dim, cn, dim, x->inv + r0, RT, C, st));
+    for (int64_t q0 = 0; q0 < nq; q0 += B, ++passes) {
+      const int64_t nb = std::min(B, nq - q0), bk = round_up(nb, 64);
+      GemmArgs g{};
+      g.A = qs.q16 + q0 * dim; g.lda = dim; g.W = x->rows + r0 * dim; g.ldw = dim;
+      g.M = (int)nb; g.N = (int)cn; g.K = dim;
+      g.rscale = qs.qinv + q0; g.cscale = x->inv + r0;
+      g.theta = lq + q0; g.theta_ld = 1; g.bias = lr ? lr + r0 : nullptr; g.lse_c = (float)(scale * 1.4426950408889634);
+      g.out = W16; g.ldo = C;
+      KCHK(gemm_cfg(false, EPI_SOFTW, -1, g, st));
+      if (out_dq && (r = grad_accumulate(W16, C, RT, C, nb, dim, ck, dq + q0 * dim, sl_q && ck % (64 * sl_q) == 0 ? sl_q : 0, part, st)))
+        return r;
+      if (out_dr) {
+        KCHK(transpose16(W16, C, nb, cn, nullptr, W16T, B, st));
+        if ((r = grad_accumulate(W16T, B, QT + q0, nqp, cn, dim, bk, drc, sl_r && bk % (64 * sl_r) == 0 ? sl_r : 0, part, st)))
+          return r;
+      }
+    }
+    if (out_dr) {
+      KCHK(scale_f32(drc, cn * dim, unscale, st));
+      if (!dr_direct) HIPCHK(copy_out(out_dr + r0 * dim, drc, (size_t)cn * dim * 4, st));
+    }
+  }
+  if (out_dq) {
+    KCHK(scale_f32(dq, nq * dim, unscale, st));
+    if (!dq_direct) HIPCHK(copy_out(out_dq, dq, (size_t)nq * dim * 4, st));
+  }
+  x->search_stats[ST_GRAD_QUERIES] += nq;
+  x->search_stats[ST_GRAD_PASSES] += passes;
+  HIPCHK(hipStreamSynchronize(st));   // workspaces are reused by the next call
+  return CLM_OK;
+}
+
+// test hooks: the EPI_SOFTW epilogue and the transposing copy alone
+int clm_gemm_softw(int hip_device, int config, const void* A, int64_t lda, const void* W, int64_t ldw, int M, int N,
+                   int K, const float* rscale, const float* cscale, const float* lq, const float* lr, float c,
+                   void* out, int64_t ldo, void* stream) {
+  if (config >= gemm_num_configs()) return fail(CLM_E_ARG, "bad config");
+  if (M < 0 || N < 0 || K <= 0 || K % 64 || lda % 8 || ldw % 8 || lda < K || ldw < K || ldo < N)
+    return fail(CLM_E_ARG, "bad shape (K % 64 == 0; lda, ldw multiples of 8 and >= K; ldo >= N)");
+  if (M == 0 || N == 0) return CLM_OK;
+  if (!A || !W || !lq || !out || ((uintptr_t)lr & 15)) return fail(CLM_E_ARG, "gemm_softw: null pointer or misaligned lr");
+  DeviceGuard g(hip_device);
+  GemmArgs a{};
+  a.A = (const u16*)A; a.lda = lda; a.W = (const u16*)W; a.ldw = ldw; a.M = M; a.N = N; a.K = K;
+  a.rscale = rscale; a.cscale = cscale; a.theta = lq; a.theta_ld = 1; a.bias = lr; a.lse_c = c; a.out = out; a.ldo = ldo;
+  hipError_t e = gemm_cfg(false, EPI_SOFTW, config, a, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(CLM_E_HIP, std::string("gemm: ") + hipGetErrorString(e));
+  return CLM_OK;
+}
+
+int clm_transpose16(int hip_device, const void* src, int64_t lds, int64_t rows, int64_t cols, const float* s,
+                    void* dst, int64_t ldd, void* stream) {
+  if (rows < 0 || cols < 0 || lds < cols || ldd < round_up(rows, 64))
+    return fail(CLM_E_ARG, "transpose16: rows, cols >= 0, lds >= cols, ldd >= round_up(rows, 64)");
+  if (rows == 0 || cols == 0) return CLM_OK;
+  if (!src || !dst) return fail(CLM_E_ARG, "transpose16: null pointer");
+  DeviceGuard g(hip_device);
+  hipError_t e = transpose16((const u16*)src, lds, rows, cols, s, (u16*)dst, ldd, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(CLM_E_HIP, std::string("transpose16: ") + hipGetErrorString(e));
   return CLM_OK;
 }

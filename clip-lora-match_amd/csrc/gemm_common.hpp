@@ -1,6 +1,6 @@
 // Shared pieces of the MFMA GEMM kernels (k_gemm.hip, k_gemm2.hip): tile geometry, counted
 // vmcnt waits, and the fused epilogues (bias / quick-GELU / fp32 residual / patch rows /
-// cosine scores / filtered candidates) from the MFMA accumulators.
+// cosine scores / filtered candidates / softmax weights) from the MFMA accumulators.
 #pragma once
 #include <algorithm>
 #include <cstdlib>
@@ -113,6 +113,19 @@ __device__ __forceinline__ void select_finish(const GemmArgs& g, const SelectRow
   }
 }
 
+// EPI_SOFTW on one score: x = sc * c as one fma with the row offset, the column term from the same
+// sc; an absent column term has the offset +inf (exp2(-inf) = 0). The sum is clamped to the largest
+// fp16 so that offsets the caller got wrong saturate instead of storing inf (v_min_f32 returns the
+// number when the sum is NaN: every stored weight is finite). Rounded to nearest even.
+constexpr float SOFTW_OFF = __builtin_inff();
+__device__ __forceinline__ float softw_val(float sc, float c, float lq, float lr) {
+  const float w = __builtin_amdgcn_exp2f(__builtin_fmaf(sc, c, -lq)) + __builtin_amdgcn_exp2f(__builtin_fmaf(sc, c, -lr));
+  return fminf(w, 65504.f);
+}
+__device__ __forceinline__ u16 softw_one(float sc, float c, float lq, float lr) {
+  return f32_to_f16(softw_val(sc, c, lq, lr));
+}
+
 // ragged-N epilogue (N or ldo not a multiple of 4): element by element, same arithmetic
 // as the vector paths (score = dot * rscale * cscale in that order; the selecting epilogues
 // through select_one / select_finish, lse_slot = the wave's slab slot)
@@ -123,7 +136,7 @@ __device__ __forceinline__ void epilogue_scalar(const GemmArgs& g, const f32x4 (
   for (int mb = 0; mb < TM; ++mb) {
     const int m = wrow + mb * 16;
     if (m >= g.M) continue;
-    const float rs = (EPI == EPI_SCORE || epi_selects(EPI)) && g.rscale ? g.rscale[m] : 1.f;
+    const float rs = (EPI == EPI_SCORE || EPI == EPI_SOFTW || epi_selects(EPI)) && g.rscale ? g.rscale[m] : 1.f;
     SelectRow sel = select_row<EPI>(g, m, epi_selects(EPI) ? g.theta[(int64_t)m * g.theta_ld] : 0.f);
     int klo = 0, khi = 0;   // FILTER_KEYS: the row's key range
     if constexpr (EPI == EPI_FILTER_KEYS) { klo = g.klo[m]; khi = g.khi[m]; }
@@ -152,6 +165,10 @@ __device__ __forceinline__ void epilogue_scalar(const GemmArgs& g, const f32x4 (
           if (g.out16) ((u16*)g.out)[(int64_t)m * g.ldo + nj] = (u16)f16_down(v);
           else ((float*)g.out)[(int64_t)m * g.ldo + nj] = v;
         }
+        else if constexpr (EPI == EPI_SOFTW)
+          ((u16*)g.out)[(int64_t)m * g.ldo + nj] =
+              softw_one(x * rs * (g.cscale ? g.cscale[nj] : 1.f), g.lse_c, g.theta[(int64_t)m * g.theta_ld],
+                        g.bias ? g.bias[nj] : SOFTW_OFF);
         else {
           static_assert(epi_selects(EPI), "unknown epilogue");
           bool open = true;
@@ -223,7 +240,7 @@ __device__ __forceinline__ void epilogue(const GemmArgs& g, const f32x4 (&acc)[B
   for (int nb = 0; nb < C::TN; ++nb) {
     if constexpr (!HOIST || epi_selects(EPI)) break;   // selecting: loaded per block, after the skip test
     const int n = wcol + nb * 16;
-    if constexpr (EPI == EPI_SCORE)
+    if constexpr (EPI == EPI_SCORE || EPI == EPI_SOFTW)
       cv[nb] = (g.cscale && n < g.N) ? *(const float4*)(g.cscale + n) : make_float4(1.f, 1.f, 1.f, 1.f);
     else
       cv[nb] = (g.bias && n < g.N) ? *(const float4*)(g.bias + n) : make_float4(0.f, 0.f, 0.f, 0.f);
@@ -346,6 +363,40 @@ __device__ __forceinline__ void epilogue(const GemmArgs& g, const f32x4 (&acc)[B
         } else {
           load_blk(mb + 1, hc);
         }
+      }
+    }
+  } else if constexpr (EPI == EPI_SOFTW) {
+    // fp16 softmax weights of the fp16-pass scores (score = dot * rscale[m] * cscale[n], EPI_SCORE's
+    // order), 8 B per lane and block. The per-column offsets (GemmArgs::bias) are loaded like cscale,
+    // one 16-byte load per block, all of them ahead of the stores; theta holds the per-row offsets.
+    float4 lr[C::TN];
+#pragma unroll
+    for (int nb = 0; nb < C::TN; ++nb) {
+      const int n = wcol + nb * 16;
+      lr[nb] = (g.bias && n < g.N) ? *(const float4*)(g.bias + n) : make_float4(SOFTW_OFF, SOFTW_OFF, SOFTW_OFF, SOFTW_OFF);
+    }
+    float rs[C::TM], lq[C::TM];
+#pragma unroll
+    for (int mb = 0; mb < C::TM; ++mb) {
+      const int m = wrow + mb * 16;
+      rs[mb] = (g.rscale && m < g.M) ? g.rscale[m] : 1.f;
+      lq[mb] = m < g.M ? g.theta[(int64_t)m * g.theta_ld] : 0.f;
+    }
+    const auto oh = buf_rsrc((const u16*)g.out + out_off + (int64_t)m0 * g.ldo, nrec);
+    const float c2 = g.lse_c;
+#pragma unroll
+    for (int mb = 0; mb < C::TM; ++mb) {
+      const int m = wrow + mb * 16;
+#pragma unroll
+      for (int nb = 0; nb < C::TN; ++nb) {
+        const int n = wcol + nb * 16;
+        const float4 c = cv[nb], l = lr[nb];
+        const uint32_t off = (m < g.M && n < g.N) ? (uint32_t)(((int64_t)(m - m0) * g.ldo + n) * 2) : BUF_OOB;
+        const float w0 = softw_val(acc[mb][nb][0] * rs[mb] * c.x, c2, lq[mb], l.x);
+        const float w1 = softw_val(acc[mb][nb][1] * rs[mb] * c.y, c2, lq[mb], l.y);
+        const float w2 = softw_val(acc[mb][nb][2] * rs[mb] * c.z, c2, lq[mb], l.z);
+        const float w3 = softw_val(acc[mb][nb][3] * rs[mb] * c.w, c2, lq[mb], l.w);
+        __builtin_amdgcn_raw_buffer_store_b64(u32x2{pack2<false>(w0, w1), pack2<false>(w2, w3)}, oh, off, 0, 0);
       }
     }
   } else {   // EPI_SCORE and the selecting epilogues: score = dot * rscale[m] * cscale[n], in this order

@@ -336,6 +336,9 @@ int pick_config(int epi, int M, int N) {
   }
   // the rank pass exists on the filter's tiles only (config 1 and G2's 8-11)
   if (epi_selects(epi) && epi != EPI_FILTER) return (forced == 1 || (forced >= 8 && forced <= 11)) ? forced : pick_from(MODELS_G2, M, N);
+  // the softmax weights exist on configs 0 and 1: 256 x 256 once its tiles fill a round of the CUs
+  if (epi == EPI_SOFTW)
+    return (forced == 0 || forced == 1) ? forced : (int64_t)((M + 255) / 256) * ((N + 255) / 256) >= 256 ? 1 : 0;
   if (forced >= 0 && forced < NCFG) return forced;
   // the search's filter GEMM (K = 512, no stores): G2's loop, 256 x 192 -- configs[4] search
   // 95.9 k QPS vs 86.4 k with gemm_kernel 256 x 256 (profiles/r04_v7_search_cfg_ab.txt)
@@ -366,6 +369,18 @@ hipError_t launch_fp16_select(int id, const GemmArgs& g, hipStream_t s) {
   return hipErrorInvalidValue;
 }
 
+// SOFTW: fp16, gemm_kernel's 128 x 128 and 256 x 256 tiles (configs 0 and 1); a call without the row
+// offsets, with misaligned column offsets or on any other config is refused
+template <bool BF>
+hipError_t launch_softw(int id, const GemmArgs& g, hipStream_t s) {
+  if constexpr (!BF) {
+    if (!g.theta || g.theta_ld < 1 || !g.out || ((uintptr_t)g.bias & 15) || g.ksplit > 1) return hipErrorInvalidValue;
+    if (id == 0) return launch_cfg<false, EPI_SOFTW, 128, 128, 2, 2, 2>(g, s);
+    if (id == 1) return launch_cfg<false, EPI_SOFTW, 256, 256, 4, 2, 2>(g, s);
+  }
+  return hipErrorInvalidValue;
+}
+
 template <bool BF>
 hipError_t dispatch(int epi, int id, const GemmArgs& g, hipStream_t s) {
   switch (epi) {
@@ -379,6 +394,7 @@ hipError_t dispatch(int epi, int id, const GemmArgs& g, hipStream_t s) {
     case EPI_LSE: return launch_fp16_select<BF, EPI_LSE>(id, g, s);
     case EPI_FILTER_MASK: return launch_fp16_select<BF, EPI_FILTER_MASK>(id, g, s);
     case EPI_FILTER_KEYS: return launch_fp16_select<BF, EPI_FILTER_KEYS>(id, g, s);
+    case EPI_SOFTW: return launch_softw<BF>(id, g, s);
     default: return hipErrorInvalidValue;
   }
 }

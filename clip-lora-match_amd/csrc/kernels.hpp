@@ -30,9 +30,15 @@ enum Epi {
   EPI_FILTER_MASK = 8,    // EPI_FILTER over the rows a bitset allows: column n is tested only where
                           // bit n & 31 of mask[n >> 5] is set (bits at or past N clear:
                           // mask_prepare). fp16, configs 1 and 8-11 only
-  EPI_FILTER_KEYS = 9     // EPI_FILTER with one open test per (row, column): column n is tested for row m
+  EPI_FILTER_KEYS = 9,    // EPI_FILTER with one open test per (row, column): column n is tested for row m
                           // only where klo[m] <= keys[n] <= khi[m] (a row with klo > khi lists nothing).
                           // fp16, configs 1 and 8-11 only
+  EPI_SOFTW = 10          // softmax weights (clm_index_softmax_grad): s as above, x = s * lse_c (lse_c = scale *
+                          // log2 e as in EPI_LSE); out16[m,n] = fp16(min(exp2(x - theta[m]) + exp2(x - bias[n]),
+                          // 65504)): theta = the per-row offsets (theta_ld apart), bias = the per-column offsets
+                          // (16-byte aligned: a lane loads its 4 at once, as it does keys), the second term
+                          // absent when bias is null (the caller folds log2 of the weights and the scaling
+                          // exponent p into the offsets); out as u16 [M, ldo]. fp16, configs 0 and 1 only
 };
 // upper bound, over the configs EPI_LSE runs on, of the slab slots per row (wave column extents are
 // 64, 96 or 128 index rows)
@@ -360,6 +366,17 @@ hipError_t lse_band_scores(const int64_t* band, const int* cnt, int64_t cap, con
 hipError_t lse_finish(const float* band_s, const int* cnt, int64_t cap, const float* part, int64_t slots,
                       const float* theta, double scale, double E, int64_t N, int64_t nq, double* lse, float* err,
                       int* redo, hipStream_t s);
+
+// ----------------------------------------------------------- softmax gradients (k_grad.hip) ---
+// dst[c, r] = fp16(float(src[r, c]) * s[r]) for r < rows, c < cols (s null: 1), src fp16 [rows, lds], dst
+// fp16 [cols, ldd]; the padding columns rows .. round_up(rows, 64) - 1 of every dst row are written as
+// zeros (ldd >= round_up(rows, 64)): dst is the K-contiguous operand of a GEMM whose K is `rows`.
+hipError_t transpose16(const u16* src, int64_t lds, int64_t rows, int64_t cols, const float* s, u16* dst, int64_t ldd,
+                       hipStream_t st);
+// EPI_SOFTW's offsets: out[i] = fp32(lse[i] * log2(e) - sub) for i < n (sub = log2 of the weight + p)
+hipError_t softw_offsets(const double* lse, int64_t n, double sub, float* out, hipStream_t st);
+// v[i] *= f for i < n
+hipError_t scale_f32(float* v, int64_t n, float f, hipStream_t st);
 
 // ----------------------------------------------------------- threshold search (k_range.hip) ---
 // The result of query q under threshold tau[q]: the rows (s, id) with rank_ahead(s, id, tau[q],

@@ -15,6 +15,9 @@ resident index (clm_index_rank), so no score matrix exists on the embeddings pat
   contrastive_loss(image_emb, text_emb, temperature)    scripts/train_lora.py:83-108 over the whole
                                                         set (or :213-241's per-batch mean), the
                                                         reference's model-selection signal
+  contrastive_loss_grad / contrastive_loss_tensor       the same loss with its gradient (what
+                                                        train_lora.py's loss.backward() delivers to
+                                                        the embeddings), streamed: no [N, N] logits
   CLIPEvaluator                                         evaluate_model.py:17-286, same method names
 
 Ranks order equal scores by candidate index (the search order); the reference's argsort leaves
@@ -237,23 +240,144 @@ def contrastive_loss(image_emb, text_emb, temperature: float = 0.07, batch_size=
         raise ValueError("temperature must be finite and positive")
     if batch_size is not None:
         return batched_loss(a, b, temperature, batch_size)
-    n = a.shape[0]
-    targets = torch.arange(n, dtype=torch.int64)
     res = {}
     for tag, qs, rows in (("i2t", a, b), ("t2i", b, a)):
-        idx = CosineIndex(rows.shape[1], capacity=n, device=device)
+        idx = CosineIndex(rows.shape[1], capacity=a.shape[0], device=device)
         try:
             idx.append(rows)
-            if int(head) <= 0 and not int(band_cap):
-                lse, t = idx.logsumexp64(qs, 1.0 / temperature, targets)
-                err = torch.zeros(n)
-            else:
-                lse, err = idx.logsumexp(qs, 1.0 / temperature, head=head, band_cap=band_cap)
-                _, t = idx.rank(qs, targets)
-            res[tag] = (lse.cpu(), err.cpu(), t.cpu())
+            res[tag] = _direction(idx, qs, temperature, head, band_cap)
         finally:
             idx.close()
+    return _loss_of(res, temperature)
+
+
+def _check_pairs(image_emb, text_emb, temperature) -> Tuple[torch.Tensor, torch.Tensor]:
+    a, b = torch.as_tensor(image_emb), torch.as_tensor(text_emb)
+    if a.dim() != 2 or b.dim() != 2 or a.shape != b.shape or a.shape[0] == 0:
+        raise ValueError(f"image_emb and text_emb must be [N >= 1, d] pairs, got {tuple(a.shape)} and {tuple(b.shape)}")
+    if not (temperature > 0 and np.isfinite(temperature)):
+        raise ValueError("temperature must be finite and positive")
+    return a, b
+
+
+def _direction(idx: CosineIndex, qs, temperature: float, head: int, band_cap: int = 0):
+    """(lse, err, pair scores) of queries qs against the index holding their partners, query i's
+    partner being row i: what contrastive_loss and contrastive_loss_grad share, on the index's device"""
+    n = qs.shape[0]
+    targets = torch.arange(n, dtype=torch.int64)
+    if int(head) <= 0 and not int(band_cap):
+        lse, t = idx.logsumexp64(qs, 1.0 / temperature, targets)
+        return lse, torch.zeros(n), t
+    lse, err = idx.logsumexp(qs, 1.0 / temperature, head=head, band_cap=band_cap)
+    _, t = idx.rank(qs, targets)
+    return lse, err, t
+
+
+def _loss_of(res, temperature: float) -> Dict[str, float]:
     return loss_from_lse(res["i2t"][0], res["t2i"][0], res["i2t"][2], temperature, res["i2t"][1], res["t2i"][1])
+
+
+# ------------------------------------------------------------------ the loss's gradient --
+def unit_gradients(dq, dr, image_unit, text_unit, temperature: float) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The loss's gradients with respect to the UNIT vectors, fp64, from the weighted sums of
+    CosineIndex.softmax_grad (images as queries, texts as the index, wq = wr = 1). With s_ij = a^_i .
+    b^_j, dL/ds_ij = (exp(s_ij / T - lse_i) + exp(s_ij / T - lse'_j)) / (2 N T) - [i = j] / (N T), so
+        g_a^_i = dq[i] / (2 N T) - b^_i / (N T),      g_b^_j = dr[j] / (2 N T) - a^_j / (N T).
+    Plain tensor arithmetic: any device."""
+    dq, dr = torch.as_tensor(dq).double(), torch.as_tensor(dr).double()
+    au, bu = torch.as_tensor(image_unit).double(), torch.as_tensor(text_unit).double()
+    n = au.shape[0]
+    return (dq / (2 * n * temperature) - bu / (n * temperature),
+            dr / (2 * n * temperature) - au / (n * temperature))
+
+
+def normalize_backward(g, x) -> torch.Tensor:
+    """Backward of x -> x / |x| (rows): (g - (g . x^) x^) / |x|, fp64"""
+    g, x = torch.as_tensor(g).double(), torch.as_tensor(x).double()
+    nrm = x.norm(dim=1, keepdim=True)
+    xu = x / nrm
+    return (g - (g * xu).sum(dim=1, keepdim=True) * xu) / nrm
+
+
+def loss_grad_from_sums(dq, dr, image_emb, text_emb, temperature: float) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(grad_image, grad_text) fp64 with respect to the raw embeddings, from softmax_grad's sums: the
+    O(N d) tail of contrastive_loss_grad (unit_gradients, then normalize_backward on each side)"""
+    a, b = torch.as_tensor(image_emb).double(), torch.as_tensor(text_emb).double()
+    ga, gb = unit_gradients(dq, dr, a / a.norm(dim=1, keepdim=True), b / b.norm(dim=1, keepdim=True), temperature)
+    return normalize_backward(ga, a), normalize_backward(gb, b)
+
+
+def contrastive_loss_grad(image_emb, text_emb, temperature: float = 0.07, head: int = 64, device=None) -> Dict:
+    """contrastive_loss and its gradient, without the [N, N] logits: {"loss", "loss_i2t", "loss_t2i",
+    "err"} as contrastive_loss computes them (the same calls: the same bits), plus
+      grad_image, grad_text   [N, d] fp32 on the GPU: dL / d(image_emb), dL / d(text_emb) with respect
+                              to the RAW, unnormalised inputs -- what autograd returns through the
+                              reference function, which normalises inside (train_lora.py:83-108);
+      rho                     the certified relative bound of the streamed sums (below).
+    Route: one log-sum-exp per direction, one CosineIndex.softmax_grad pass (wq = wr = 1) over the text
+    index with the images as queries, then O(N d) tensor ops: the factor 1 / (2 N T), the diagonal
+    term and the normalise backward (loss_grad_from_sums).
+    Accuracy: row i of grad_image is within (rho * A_i + tau) / (2 N T |image_i|) of the exact
+    gradient in the 2-norm, A_i = sum_j (exp(s_ij / T - lse_i) + exp(s_ij / T - lse'_j)) the row's
+    weight mass (grad_text alike), (rho, tau) from search.softmax_grad_bound widened by exp(the
+    largest log-sum-exp bound). rho is the honest worst case -- every fp16-pass score off by its whole
+    bound in the same direction: 0.038 at T = 0.07, 0.28 at T = 0.01; measured errors sit near 1e-3 of
+    A (DESIGN.md)."""
+    from .search import softmax_grad_bound
+    a, b = _check_pairs(image_emb, text_emb, temperature)
+    n = a.shape[0]
+    res = {}
+    txt = CosineIndex(b.shape[1], capacity=n, device=device)
+    try:
+        txt.append(b)
+        res["i2t"] = _direction(txt, a, temperature, head)
+        img = CosineIndex(a.shape[1], capacity=n, device=device)
+        try:
+            img.append(a)
+            res["t2i"] = _direction(img, b, temperature, head)
+        finally:
+            img.close()
+        dq, dr = txt.softmax_grad(a, 1.0 / temperature, res["i2t"][0], row_lse=res["t2i"][0], wq=1.0, wr=1.0)
+        dev = txt.device
+    finally:
+        txt.close()
+    out = _loss_of(res, temperature)
+    ga, gb = loss_grad_from_sums(dq, dr, a.to(dev), b.to(dev), temperature)
+    rho, _ = softmax_grad_bound(1.0 / temperature, n)
+    lse_err = max(float(torch.as_tensor(res["i2t"][1]).max()), float(torch.as_tensor(res["t2i"][1]).max()))
+    out.update(grad_image=ga.float(), grad_text=gb.float(), rho=(1 + rho) * float(np.exp(lse_err)) - 1)
+    return out
+
+
+class ContrastiveLoss(torch.autograd.Function):
+    """contrastive_loss_grad as an autograd node: forward returns the loss as a 0-dim tensor on the
+    inputs' device and keeps the two gradients, backward hands them on times the upstream gradient,
+    so loss.backward() reaches whatever torch module produced the embeddings."""
+
+    @staticmethod
+    def forward(ctx, image_emb, text_emb, temperature=0.07, head=64):
+        r = contrastive_loss_grad(image_emb.detach(), text_emb.detach(), temperature, head)
+        ctx.save_for_backward(r["grad_image"].to(device=image_emb.device, dtype=image_emb.dtype),
+                              r["grad_text"].to(device=text_emb.device, dtype=text_emb.dtype))
+        return torch.tensor(r["loss"], dtype=image_emb.dtype, device=image_emb.device)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        ga, gb = ctx.saved_tensors
+        return grad_out.to(ga.device) * ga, grad_out.to(gb.device) * gb, None, None
+
+
+def contrastive_loss_tensor(image_emb, text_emb, temperature: float = 0.07, head: int = 64) -> torch.Tensor:
+    """The contrastive loss of N pairs as a differentiable 0-dim tensor (ContrastiveLoss): the
+    training-side twin of contrastive_loss. image_emb / text_emb: [N, d] floating-point tensors, raw
+    or normalised; the whole set is one global batch (the per-batch validation number stays
+    contrastive_loss(batch_size=))."""
+    if not (isinstance(image_emb, torch.Tensor) and isinstance(text_emb, torch.Tensor)):
+        raise ValueError("image_emb and text_emb must be tensors")
+    if not (image_emb.is_floating_point() and text_emb.is_floating_point()):
+        raise ValueError("image_emb and text_emb must be floating-point tensors")
+    _check_pairs(image_emb, text_emb, temperature)
+    return ContrastiveLoss.apply(image_emb, text_emb, float(temperature), int(head))
 
 
 # ------------------------------------------------------------------ similarity matrix -> ranks --
@@ -379,4 +503,6 @@ class CLIPEvaluator:
 
 
 __all__ = ["retrieval_ranks", "recall_at_k", "mrr", "mean_average_precision", "evaluate_retrieval",
-           "matching_accuracy", "threshold_metrics", "evaluate_threshold_retrieval", "contrastive_loss", "loss_from_lse", "batched_loss", "read_pairs", "CLIPEvaluator"]
+           "matching_accuracy", "threshold_metrics", "evaluate_threshold_retrieval", "contrastive_loss", "loss_from_lse", "batched_loss", "read_pairs", "CLIPEvaluator",
+           "contrastive_loss_grad", "contrastive_loss_tensor", "ContrastiveLoss", "unit_gradients", "normalize_backward",
+           "loss_grad_from_sums"]

@@ -60,6 +60,35 @@ def _pad_dim(x: torch.Tensor, dim_p: int) -> torch.Tensor:
     return torch.nn.functional.pad(x, (0, dim_p - x.shape[-1]))
 
 
+# |fp16-pass score - exact cosine| for dim <= 8192 (LSE_E in csrc/capi_search.cpp; DESIGN.md derives it)
+PASS_E = 1.95e-3 + 4.9e-4 + 1e-6
+
+
+def softmax_grad_bound(scale: float, n_terms: int, wq: float = 1.0, wr: float = 1.0, dim: Optional[int] = None):
+    """(rho, tau) of CosineIndex.softmax_grad: per output row ||computed - true|| <= rho * A + tau, A =
+    the row's weight mass, n_terms = the terms summed into the row (N for dq, nq for dr). DESIGN.md
+    derives every factor:
+      the weights' scores   expm1(scale * E + eps_x); dim=None: E = PASS_E against the caller's own
+                            rows (the certified bound); dim given: E = dim * 2^-24 + 1e-6 against the
+                            fp64 value from the same fp16 operands (the tight bound);
+                            eps_x = 2^-24 (4.04 scale + 70) + 2^-23: the exponent's fp32 forming, v_exp_f32
+      W's rounding to fp16  2^-11
+      the operand           certified: 3 * 2^-11 (rounded to fp16 when stored, renormalised by the
+                            inverse norm of the rounded row, re-rounded by the transposing copy);
+                            tight: 2^-11 (the copy's re-rounding alone)
+      fp32 accumulation     (n_terms / 32 + n_terms / 64 + 16) 2^-24: MFMA steps, chunk and slice sums
+    tau = n_terms * 2^-14 * (wq + wr) * exp(2 scale PASS_E) / 65504: weights below fp16's normal range
+    (under 9.3e-10 of the largest possible one) may lose everything."""
+    e_score = PASS_E if dim is None else dim * 2.0 ** -24 + 1e-6
+    eps_x = 2.0 ** -24 * (4.04 * scale + 70.0) + 2.0 ** -23
+    e1 = math.expm1(scale * e_score + eps_x)
+    u = 2.0 ** -11
+    acc = (n_terms / 32 + n_terms / 64 + 16) * 2.0 ** -24
+    rho = (1 + e1) * (1 + u) * (1 + (3 * u if dim is None else u) + acc) - 1
+    tau = n_terms * 2.0 ** -14 * (wq + wr) * math.exp(2 * scale * PASS_E) / 65504
+    return rho, tau
+
+
 def pack_mask(keep: torch.Tensor) -> torch.Tensor:
     """bool [N] -> the ceil(N / 32) little-endian uint32 words of a row filter (bit j & 31 of word
     j >> 5 = keep[j]; the bits past N clear), stored as int32 on keep's device"""
@@ -776,6 +805,56 @@ class CosineIndex:
         v = (ctypes.c_int64 * 14)()
         C.check(C.lib().clm_index_stats2(self._h, v, 14))
         return {"fast": v[11], "exact": v[12], "overflow": v[13]}
+
+    # ------------------------------------------------------------ softmax gradients --
+    def softmax_grad(self, queries, scale: float, lse, row_lse=None, wq: float = 1.0, wr: float = 1.0,
+                     want_rows: bool = True, chunk_rows: int = 0, query_block: int = 0):
+        """(dq [nq, dim] f32, dr [N, dim] f32 or None) on the GPU: the softmax-weighted sums over the
+        index, both ways, without a [nq, N] matrix (clm_index_softmax_grad). With unit vectors q^_i,
+        r^_j and s_ij = q^_i . r^_j,
+            W_ij = wq * exp(scale * s_ij - lse[i]) + wr * exp(scale * s_ij - row_lse[j]),
+        dq[i] = sum_j W_ij r^_j and dr[j] = sum_i W_ij q^_i, dr in local row order (want_rows=False: not
+        computed). lse [nq] as `logsumexp` returns it; row_lse [N] the log-sum-exp of each index row
+        over the queries. One direction: wr = 0 and no row_lse -- with wq = 1, dq is the softmax read-out
+        of the index and dr its adjoint; with both terms it is all of the symmetric contrastive loss's
+        gradient but its diagonal.
+        The scores inside W are fp16-pass scores: per output row ||computed - true|| <= rho * A + tau, A
+        the row's weight mass sum W_ij, (rho, tau) = softmax_grad_bound(...) -- rho = 0.038 at scale 1 /
+        0.07 and 0.28 at 100 in the certified worst case (every score off by the pass's whole bound E the
+        same way); measured ratios sit near 1e-3 (DESIGN.md). Two identical calls return the same bits;
+        the bits may depend on nq, chunk_rows and query_block (index rows / queries per pass; 0 =
+        default). ValueError: an empty index, a scale that is not finite and positive, a negative
+        weight, wr > 0 without row_lse, lse of the wrong length, a zero row in the index or a zero query
+        (the reference's gradient is NaN there)."""
+        q = self._queries(queries)
+        nq, n = q.shape[0], len(self)
+        l = torch.as_tensor(lse).to(device=self.device, dtype=torch.float64).contiguous()
+        if l.shape != (nq,):
+            raise ValueError(f"lse must be [{nq}], got {tuple(l.shape)}")
+        rl = None
+        if row_lse is not None:
+            rl = torch.as_tensor(row_lse).to(device=self.device, dtype=torch.float64).contiguous()
+            if rl.shape != (n,):
+                raise ValueError(f"row_lse must be [{n}], got {tuple(rl.shape)}")
+        if int(chunk_rows) < 0 or int(query_block) < 0:
+            raise ValueError("chunk_rows and query_block must not be negative")
+        dq = torch.empty((nq, self.dim_p), dtype=torch.float32, device=self.device)
+        dr = torch.empty((n, self.dim_p), dtype=torch.float32, device=self.device) if want_rows else None
+        code = C.CLM_F32 if q.dtype == torch.float32 else C.CLM_F16
+        C.check(C.lib().clm_index_softmax_grad(self._h, C.ptr(q), code, nq, float(scale), C.ptr(l),
+                                               C.ptr(rl) if rl is not None else None, float(wq), float(wr),
+                                               C.ptr(dq), C.ptr(dr) if dr is not None else None, int(chunk_rows),
+                                               int(query_block), C.stream_of(self.device)), "clm_index_softmax_grad")
+        if self.dim_p != self.dim:
+            dq = dq[:, :self.dim].contiguous()
+            dr = dr[:, :self.dim].contiguous() if dr is not None else None
+        return dq, dr
+
+    def grad_stats(self) -> dict:
+        """softmax_grad queries served (`queries`) and the (query block, row chunk) passes run (`passes`)"""
+        v = (ctypes.c_int64 * 24)()
+        C.check(C.lib().clm_index_stats2(self._h, v, 24))
+        return {"queries": v[22], "passes": v[23]}
 
     # ------------------------------------------------------------ shard file --
     def save_shard(self, path: Union[str, Path], meta: Optional[dict] = None, chunk_rows: int = 1 << 20) -> None:

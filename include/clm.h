@@ -29,6 +29,10 @@
  *                              normaliser of softmax match probabilities, without a [nq, N] matrix
  *   clm_index_lse64            (new) the same reduction and the pair scores on unrounded fp64
  *                              cosines: that function on float64 tensors
+ *   clm_index_softmax_grad     (new) the softmax-weighted sums over the index, both ways: what
+ *                              loss.backward() of that function (scripts/train_lora.py:83-108 as
+ *                              called from its training loop) delivers to the embeddings, without the
+ *                              [N, N] logits
  *   clm_index_search_above     (new) every index row at or above a cosine, exactly: the relevant set
  *                              of scripts/evaluate.py:141-269 (evaluate_single_query: cosine >= 0.7),
  *                              "which reports describe the same item", near-duplicate listing
@@ -295,6 +299,32 @@ int clm_index_lse(clm_index* idx, const void* q, int q_dtype, int64_t nq, double
 int clm_index_lse64(clm_index* idx, const void* q, int q_dtype, int64_t nq, double scale, const int64_t* target,
                     double* out_lse, double* out_pair, void* stream);
 
+/* Softmax-weighted sums over the index, both ways: what the gradient of a softmax / InfoNCE loss over
+ * the index needs, with nothing sized nq x size. With unit vectors q^_i, r^_j, s_ij = q^_i . r^_j and
+ *   W_ij = wq * exp(scale * s_ij - q_lse[i]) + wr * exp(scale * s_ij - row_lse[j])
+ * (the wr term absent when row_lse is NULL):
+ *   out_dq[i] = sum_j W_ij r^_j   [nq, dim] fp32,      out_dr[j] = sum_i W_ij q^_i   [size, dim] fp32
+ * in local row order; either output may be NULL. q_lse [nq] / row_lse [size] are log-sum-exps in
+ * doubles as clm_index_lse returns them (q_lse of the queries over the index, row_lse of each index
+ * row over the queries), expected within scale * E of the true ones, E = 2.441e-3 the fp16 pass's
+ * score bound: weights far above what such offsets allow saturate at the fp16 maximum instead of
+ * overflowing. The scores inside W are fp16-pass scores: per output row the 2-norm of the error is at
+ * most rho times the row's weight mass plus tau, rho = expm1(scale * E) and about 2e-3 more for the fp16
+ * roundings (DESIGN.md states every term: 0.038 at scale 1 / 0.07, 0.28 at 100 in the worst case;
+ * measured values sit near 1e-3), tau = terms * 2^-14 * (wq + wr) * exp(2 scale E) / 65504 for the weights
+ * below fp16's normal range. No floating-point atomics: two
+ * identical calls return the same bits; the bits may depend on nq, chunk_rows and query_block.
+ * chunk_rows / query_block: index rows / queries per pass, rounded up to multiples of 64; 0 = default
+ * (bounded by $CLM_SEARCH_WS_MB and a quarter of the free device memory). Every pointer host or device.
+ * CLM_E_ARG: an empty index, a null q or q_lse, a dtype other than f32 / f16, nq < 0, a scale that is
+ * not finite and positive, a negative or non-finite weight, wr > 0 without row_lse, dim > 8192, size >
+ * 2^31 - 1, an index row or a query whose norm is zero or not finite (the reference's gradient is NaN
+ * there). nq == 0 returns at once. clm_index_stats2 entries 22 / 23 count the queries served and the
+ * (query block, row chunk) passes run. */
+int clm_index_softmax_grad(clm_index* idx, const void* q, int q_dtype, int64_t nq, double scale,
+                           const double* q_lse, const double* row_lse, double wq, double wr, float* out_dq,
+                           float* out_dr, int64_t chunk_rows, int64_t query_block, void* stream);
+
 /* Threshold search: WHICH rows score at or above a threshold. With s_j the exact score of row j (as
  * clm_index_search returns it) and tau = threshold[i] (one fp32 per query), the result of query i is
  *
@@ -402,7 +432,7 @@ int clm_index_search_keyed(clm_index* idx, const void* q, int q_dtype, int64_t n
  * bounded queries whose candidate list overflowed (redone by a whole-list pass, or by the exact
  * scan when the list is longer than 8192 / k chunks of 4096) */
 int clm_index_stats(const clm_index* idx, int64_t* filtered, int64_t* exact, int64_t* overflow);
-/* out[0..n), n <= 22: sampled bounded, fp16-scan bounded, full exact scan, overflow re-runs, then the
+/* out[0..n), n <= 24: sampled bounded, fp16-scan bounded, full exact scan, overflow re-runs, then the
  * sampled queries whose filter pass ran on the G2 256 x 192 tiles / on gemm_kernel 256 x 256 (chosen
  * per query block from the block's sampled candidate counts: near-duplicate blocks take the latter),
  * then the queries served by the small-batch streaming search (nq <= 16 on a large index: one pass
@@ -414,7 +444,8 @@ int clm_index_stats(const clm_index* idx, int64_t* filtered, int64_t* exact, int
  * those whose candidate list overflowed its capacity, then the clm_index_search_masked queries served
  * by the pass route, by the gather route and by the exact route (a pass-route query redone exactly
  * counts as exact), then (entries 20 / 21) the clm_index_search_keyed queries served by the pass route
- * and by the exact route (a redone query counts as exact) */
+ * and by the exact route (a redone query counts as exact), then (entries 22 / 23) the
+ * clm_index_softmax_grad queries served and the (query block, row chunk) passes run for them */
 int clm_index_stats2(const clm_index* idx, int64_t* out, int n);
 
 /* full cosine matrix, exact: out [nq, n] f32 = fp32(cos64(q_i, c_j)), any dim */
@@ -501,6 +532,23 @@ int clm_gemm_select_keyed(int hip_device, int config, const void* A, int64_t lda
                           int64_t theta_ld, int* cnt, float* cand_s, int64_t* cand_i, int cap, int64_t base,
                           const uint32_t* cbound, const int32_t* keys, const int32_t* klo, const int32_t* khi,
                           int m_fastest, void* stream);
+/* clm_gemm_softw: the softmax-weight epilogue alone (test hook; fp16 A [M, lda] / W [N, ldw], device
+ * pointers). s = acc * rscale[m] * cscale[n] (either NULL: 1), x = s * c:
+ *   out[m * ldo + n] = fp16(min(exp2(x - lq[m]) + exp2(x - lr[n]), 65504))   (lr NULL: the first term alone)
+ * lq [M], lr [N] fp32 (lr 16-byte aligned); out u16 [M, ldo >= N]; rows at or past M and columns at or
+ * past N are untouched. Configs 0 and 1 (-1: heuristic); any other is CLM_E_HIP with nothing written.
+ * CLM_E_ARG: config >= clm_gemm_num_configs(), M or N < 0, K <= 0 or K % 64, lda / ldw not a multiple
+ * of 8 or below K, ldo < N, and with M, N > 0 a null A, W, lq or out, or a misaligned lr.
+ * clm_transpose16: dst[c * ldd + r] = fp16(float(src[r * lds + c]) * s[r]) for r < rows, c < cols (s
+ * NULL: 1; fp16 src / dst, fp32 s, device pointers); columns rows .. round_up(rows, 64) - 1 of every dst
+ * row are written as zeros. CLM_E_ARG: rows or cols < 0, lds < cols, ldd < round_up(rows, 64), and with
+ * rows, cols > 0 a null src or dst. */
+enum { CLM_EPI_SOFTW = 10 };
+int clm_gemm_softw(int hip_device, int config, const void* A, int64_t lda, const void* W, int64_t ldw, int M, int N,
+                   int K, const float* rscale, const float* cscale, const float* lq, const float* lr, float c,
+                   void* out, int64_t ldo, void* stream);
+int clm_transpose16(int hip_device, const void* src, int64_t lds, int64_t rows, int64_t cols, const float* s,
+                    void* dst, int64_t ldd, void* stream);
 /* diagnostic flags (micro-benchmarks and tests only; 0 in production), initialised from
  * $CLM_GEMM_DEBUG: for later clm_gemm / clm_gemm_select calls bit 0 = skip the epilogue (accumulators kept
  * live), bit 1 = run the epilogue but drop every store, bit 2 = one tile per workgroup
