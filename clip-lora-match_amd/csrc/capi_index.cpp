@@ -228,12 +228,15 @@ static int64_t mutate_chunk_rows(size_t row_bytes) {
   return r;
 }
 
-// the caller's global ids (host or device) as local rows on the host; CLM_E_ARG for one outside the index
+// the caller's global ids (host or device) as local rows on the host; CLM_E_ARG for one outside the index.
+// Device ids are read in stream order on st (the caller's stream may still be writing them: a plain
+// hipMemcpy runs on the null stream, which a non-blocking stream does not wait for); drains st.
 static int mutate_local_ids(const clm_index* x, const int64_t* ids, int64_t n, std::vector<int64_t>& loc,
-                            const char* what) {
+                            const char* what, hipStream_t st) {
   loc.resize((size_t)n);
-  if (is_device_ptr(ids)) HIPCHK(hipMemcpy(loc.data(), ids, (size_t)n * 8, hipMemcpyDeviceToHost));
+  if (is_device_ptr(ids)) HIPCHK(hipMemcpyAsync(loc.data(), ids, (size_t)n * 8, hipMemcpyDeviceToHost, st));
   else std::memcpy(loc.data(), ids, (size_t)n * 8);
+  HIPCHK(hipStreamSynchronize(st));
   for (int64_t& v : loc) {
     if (v < x->offset || v - x->offset >= x->n)
       return fail(CLM_E_ARG, std::string(what) + ": id " + std::to_string(v) + " is outside [offset, offset + size)");
@@ -248,12 +251,11 @@ int clm_index_remove(clm_index* x, const int64_t* ids, int64_t n_ids, void* stre
   DeviceGuard g(x->dev);
   hipStream_t st = (hipStream_t)stream;
   std::vector<int64_t> rem;
-  int r = mutate_local_ids(x, ids, n_ids, rem, "index remove");
+  int r = mutate_local_ids(x, ids, n_ids, rem, "index remove", st);
   if (r) return r;
   std::sort(rem.begin(), rem.end());
   rem.erase(std::unique(rem.begin(), rem.end()), rem.end());
   const int64_t m = (int64_t)rem.size(), n = x->n, dim = x->dim;
-  HIPCHK(hipStreamSynchronize(st));
   if ((r = mutate_stage(x))) return r;
   x->samp_n = -1;
   x->inv_keys_n = -1;
@@ -310,7 +312,7 @@ int clm_index_update(clm_index* x, const int64_t* ids, const void* rows, int dty
   DeviceGuard g(x->dev);
   hipStream_t st = (hipStream_t)stream;
   std::vector<int64_t> loc;
-  int r = mutate_local_ids(x, ids, n, loc, "index update");
+  int r = mutate_local_ids(x, ids, n, loc, "index update", st);
   if (r) return r;
   {
     std::vector<int64_t> s(loc);
@@ -318,7 +320,6 @@ int clm_index_update(clm_index* x, const int64_t* ids, const void* rows, int dty
     if (std::adjacent_find(s.begin(), s.end()) != s.end()) return fail(CLM_E_ARG, "index update: duplicate id");
   }
   const int64_t dim = x->dim;
-  HIPCHK(hipStreamSynchronize(st));
   if ((r = mutate_stage(x))) return r;
   if (dtype == CLM_F32 && !x->rows32 && (r = start_rows32(x, st))) return r;
   x->samp_n = -1;   // n stays: nothing else would rebuild the sample and the order keys
@@ -382,7 +383,9 @@ int clm_index_read(clm_index* x, int64_t start, int64_t n, float* dst, void* str
     for (size_t i = 0; i < cnt; ++i) f[i] = host_f16_to_f32(h[i]);
   }
   if (is_device_ptr(dst)) {
-    HIPCHK(hipMemcpy(dst, f.data(), cnt * 4, hipMemcpyHostToDevice));
+    // on st, behind whatever the caller's stream wrote to dst before; f is freed on return
+    HIPCHK(hipMemcpyAsync(dst, f.data(), cnt * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));
   } else {
     std::memcpy(dst, f.data(), cnt * 4);
   }

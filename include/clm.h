@@ -61,6 +61,10 @@
  *     buffers are staged through the context's device workspace.
  *   - `stream` is a hipStream_t (NULL = the legacy default stream). Calls are
  *     asynchronous w.r.t. the host only when every buffer is device memory.
+ *     Device inputs are read and device outputs written in stream order on
+ *     `stream`: work queued on it before the call is seen, work queued after
+ *     sees the results, and the caller needs no other synchronisation (a
+ *     non-blocking stream included; tests/test_gpu_stream_order.py).
  *   - one context per device; calls on one context must be externally
  *     serialised; different contexts are independent.
  */
